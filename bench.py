@@ -13,16 +13,21 @@ N GPUs (torchrun, one process per GPU):
   * headline `value` (--shard nodes, the default): ONE 100k-node cluster split into N
     contiguous name-rank shards, one per GPU; each pod is decided jointly through the per-pod
     exchange over xGMI (ksim_shard_*), the owning rank commits.  pods/s of that one cluster
-    (scaling "strong"); placements checked against a single-GPU run of the same queue.
-  * `replicas`: every rank schedules its own cluster under its own LeastRequested weight (a
+    (scaling "strong"); with --full, placements checked against a single-GPU run of the same queue.
+  * `replicas` (--full): every rank schedules its own cluster under its own LeastRequested weight (a
     what-if sweep, no data-path collective; scaling "weak").  --shard replicas makes it the
     headline instead.
 
 The JSON line carries the roofline of the dominant kernel (algorithmic bytes per launch ÷ the
 HIP-event launch duration measured on the library's stream, against the 8 TB/s HBM peak; null
-for tree mode, whose kernel does not read the table per pod) and a cpu_baseline: the C port of
-the Go path (oracle/cpu_ref.c) timed on the host on bounded prefixes of the same queue at 1, 16
-and all threads, its placements equal to the GPU's for the same prefix ("parity").
+for tree mode, whose kernel does not read the table per pod).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what is
+measured beside the headline: the tree-mode line, the C4 streaming side line (c3), the per_pod
+line (c2 / c2x), with N > 1 the single-GPU parity reference and the replica side line, and a
+cpu_baseline: the C port of the Go path (oracle/cpu_ref.c) timed on the host on bounded prefixes
+of the same queue at 1, 16 and all threads, its placements equal to the GPU's for the same prefix
+("parity").  --dump-outputs DIR writes the last timed step's placements to DIR/placements.npy.
 """
 import argparse
 import json
@@ -94,6 +99,26 @@ def effective_cpus():
     return n
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: most bytes written over all arrays (kept under 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> what the last timed step returned) as
+    float64 in path/<name>.npy.  An array beyond its share of DUMP_BYTES is cut to a fixed sample
+    of its rows (seed 0, ascending), whose indices go to path/<name>_rows.npy beside it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        row_bytes = 8 * max(1, arr[0].size if arr.ndim > 1 and len(arr) else 1)
+        if arr.size * 8 > share:
+            rows = np.sort(np.random.default_rng(0).choice(len(arr), size=max(1, share // row_bytes), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            arr = arr[rows]
+        np.save(os.path.join(path, name + ".npy"), arr.astype(np.float64))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,16 +129,23 @@ def parse():
     ap.add_argument("--nodes", type=int, default=None, help="default: c3 100,000, c2 5,000, c4 1,000,000")
     ap.add_argument("--pods", type=int, default=None, help="queue length (default: c3 1M, c2 50k, c4 as needed)")
     ap.add_argument("--mode", default="auto", choices=["auto", "launch", "persistent", "tree"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured beside the headline: the tree-mode line, the C4 streaming side "
+                         "line, the per_pod line, the CPU baseline with its parity check and, with N > 1, the "
+                         "single-GPU reference and the replica side line (each tuned by its own option below); "
+                         "without it only the headline steps are run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64)")
     ap.add_argument("--no-tree", dest="tree", action="store_false",
-                    help="skip the tree-mode line measured beside the scan (c3/c4)")
+                    help="--full: skip the tree-mode line measured beside the scan (c3/c4)")
     ap.add_argument("--cpu-sample", type=int, default=30000,
-                    help="most pods in a CPU-baseline prefix (0 = skip); each leg is sized to ~8 s of CPU work")
+                    help="--full: most pods in a CPU-baseline prefix (0 = skip); each leg is sized to ~8 s of CPU work")
     ap.add_argument("--c4-pods", type=int, default=20000,
-                    help="c3 line: pods of the 1M-node C4 streaming side measurement (0 = skip)")
+                    help="--full, c3 line: pods of the 1M-node C4 streaming side measurement (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--per-pod-calls", type=int, default=200,
-                    help="c2 / c2x: timed ksim_k8s_cache_schedule calls through the C++ scheduler cache at each "
-                         "cached-pod mark (0 = skip the per_pod side line)")
+                    help="--full, c2 / c2x: timed ksim_k8s_cache_schedule calls through the C++ scheduler cache at "
+                         "each cached-pod mark (0 = skip the per_pod side line)")
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "c2x", "c4", "c5"],
                     help="c3: the headline metric (default); c2: 5k heterogeneous nodes with selectors, "
                          "ports and taints; c4: 1M nodes; c5: the 4,096-scenario policy sweep")
@@ -124,8 +156,9 @@ def parse():
     ap.add_argument("--sweep-pods", type=int, default=5000, help="c5: pods scheduled in every scenario")
     ap.add_argument("--shard", default="nodes", choices=["nodes", "replicas", "none"],
                     help="N>1 headline: one node-sharded cluster (strong, default) or per-rank replicas "
-                         "(weak); the other one is measured beside it unless 'none'")
-    ap.add_argument("--replica-pods", type=int, default=200_000, help="N>1: queue prefix of the replica side line")
+                         "(weak); with --full the other one is measured beside it unless 'none'")
+    ap.add_argument("--replica-pods", type=int, default=200_000,
+                    help="--full, N>1: queue prefix of the replica side line")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank on device 0 (gloo), grids split so the "
                          "ranks' persistent kernels are co-resident")
@@ -134,10 +167,17 @@ def parse():
     for k in ("steps", "warmup", "nodes", "pods"):
         if getattr(a, k) is None:
             setattr(a, k, d.get(k))
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.batch is None:
         a.batch = d.get("batch") or -(-a.pods // a.steps)
     if a.pods is None:
         a.pods = a.steps * a.batch
+    if a.workload != "c5" and a.steps > a.pods:
+        ap.error("--steps must be at most the queue length")
+    if not a.full:  # the headline alone
+        a.tree = False
+        a.cpu_sample = a.c4_pods = a.per_pod_calls = 0
     return a
 
 
@@ -153,14 +193,26 @@ WORKLOADS = {
 }
 
 
+def device_sync():
+    """hipDeviceSynchronize on this thread's device, through the HIP runtime libksim.so is linked
+    against (a library handle resolves its dependencies' symbols too), so that a single-process
+    run pays for no torch import."""
+    from ksim import abi
+    rc = abi.lib().hipDeviceSynchronize()
+    if rc:
+        raise RuntimeError("hipDeviceSynchronize: HIP error %d" % rc)
+
+
 class Dist:
     """torchrun environment: one process per GPU over RCCL, or (--one-device) every rank on
-    device 0 over gloo, the rehearsal a 1-GPU box allows."""
+    device 0 over gloo, the rehearsal a 1-GPU box allows.  torch is imported for N > 1 only."""
 
     def __init__(self, a):
-        import torch
-        self.torch = torch
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
+        self.torch = None
+        if self.world > 1:
+            import torch
+            self.torch = torch
         self.rank = int(os.environ.get("RANK", "0"))
         self.local = int(os.environ.get("LOCAL_RANK", "0"))
         self.one = a.one_device
@@ -179,9 +231,10 @@ class Dist:
                 dist.init_process_group("nccl")
 
     def sync(self):
+        if self.dist is None:
+            return device_sync()
         self.torch.cuda.synchronize()
-        if self.dist is not None:
-            self.dist.barrier()
+        self.dist.barrier()
         self.torch.cuda.synchronize()
 
     def barrier(self):
@@ -210,9 +263,16 @@ class Dist:
 
 def timed_queue(a, D, make, steps, batch, pods):
     """Warm up on a separate scheduler (make()), then time `steps` calls of `batch` pods over the
-    first `pods` pods of a fresh one, bracketed by barrier + device sync on every rank.
-    Returns (placements, elapsed max over ranks, summed kernel ms, launches, last stats)."""
+    first `pods` pods of a fresh one, bracketed by barrier + device sync on every rank.  Exactly
+    `steps` calls are timed: when `steps` batches would run past the queue's end, the queue is
+    cut into `steps` slices as even as integers allow (of `batch` pods each when that divides it).
+    Returns (scheduler, placements, elapsed max over ranks, summed kernel ms, launches, last
+    stats, pods timed, pods of the last step)."""
     import numpy as np
+    if steps * batch >= pods:
+        edges = [i * pods // steps for i in range(steps + 1)]
+    else:
+        edges = [i * batch for i in range(steps + 1)]
     w = make()
     first = 0
     for _ in range(a.warmup):
@@ -225,18 +285,15 @@ def timed_queue(a, D, make, steps, batch, pods):
     outs, first, kms, launches, st = [], 0, 0.0, 0, None
     D.sync()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        cnt = min(batch, pods - first)
-        if cnt <= 0:
-            break
+    for i in range(steps):
+        first, cnt = edges[i], edges[i + 1] - edges[i]
         o, _, st = g.schedule(first, cnt)
         outs.append(o)
-        first += cnt
         kms += st.kernel_ms
         launches += st.kernel_launches
     D.sync()
     el = D.allmax(time.perf_counter() - t0)
-    return g, np.concatenate(outs), el, kms, launches, st, first
+    return g, np.concatenate(outs), el, kms, launches, st, edges[-1], len(outs[-1])
 
 
 class Local:
@@ -244,10 +301,7 @@ class Local:
     barrier = staticmethod(lambda: None)
     allmax = staticmethod(lambda x: x)
 
-    @staticmethod
-    def sync():
-        import torch
-        torch.cuda.synchronize()
+    sync = staticmethod(device_sync)
 
 
 def single_cluster(a, D, cl, preds, prios, mode, device):
@@ -255,9 +309,10 @@ def single_cluster(a, D, cl, preds, prios, mode, device):
     single-GPU reference for the node-sharded run with D = Local)."""
     from ksim import scheduler
     make = lambda: scheduler.GenericScheduler(cl, preds, prios, device=device, mode=mode, collect_reasons=False)
-    g, out, el, kms, launches, st, pods = timed_queue(a, D, make, a.steps, a.batch, a.pods)
+    g, out, el, kms, launches, st, pods, last = timed_queue(a, D, make, a.steps, a.batch, a.pods)
     g.close()
-    return dict(out=out, elapsed=el, kernel_ms=kms, launches=launches, mode=st.mode, blocks=st.blocks, pods=pods)
+    return dict(out=out, elapsed=el, kernel_ms=kms, launches=launches, mode=st.mode, blocks=st.blocks, pods=pods,
+                last=last)
 
 
 def node_sharded(a, D, cl, preds, prios):
@@ -278,9 +333,9 @@ def node_sharded(a, D, cl, preds, prios):
     err = None
     res = None
     try:
-        g, out, el, kms, launches, st, pods = timed_queue(a, D, make, a.steps, a.batch, a.pods)
+        g, out, el, kms, launches, st, pods, last = timed_queue(a, D, make, a.steps, a.batch, a.pods)
         res = dict(out=out, elapsed=el, kernel_ms=D.allmax(kms), launches=launches, mode=st.mode, blocks=st.blocks,
-                   pods=pods, nodes_local=g.hi - g.lo)
+                   pods=pods, nodes_local=g.hi - g.lo, last=last)
     except Exception as e:  # noqa: BLE001 — reported in the JSON line
         err = "%s: %s" % (type(e).__name__, e)
     errs = D.gather(err)
@@ -301,7 +356,7 @@ def tree_mode(a, cl, preds, prios, device, ref):
     from ksim import abi, scheduler
 
     make = lambda: scheduler.GenericScheduler(cl, preds, prios, device=device, mode=abi.MODE_TREE, collect_reasons=False)
-    g, out, el, kms, launches, st, pods = timed_queue(a, Local, make, a.steps, a.batch, a.pods)
+    g, out, el, kms, launches, st, pods, _ = timed_queue(a, Local, make, a.steps, a.batch, a.pods)
     g.close()
     return {"value": round(pods / el, 1), "unit": "pods/s", "ms_per_step": round(el * 1e3 / a.steps, 4),
             "kernel_us_per_pod": round(kms * 1e3 / pods, 3),
@@ -376,7 +431,7 @@ def c4_stream_side(a):
     a4 = argparse.Namespace(**vars(a))
     a4.warmup = 1
     make = lambda: scheduler.GenericScheduler(cl, preds, prios, device=0, collect_reasons=False)
-    g, out, el, kms, launches, st, pods = timed_queue(a4, Local, make, steps, batch, P)
+    g, out, el, kms, launches, st, pods, _ = timed_queue(a4, Local, make, steps, batch, P)
     g.close()
     avg = kms / 1e3 / max(launches, 1)
     achieved = 60 * n * batch / avg / 1e9
@@ -437,8 +492,8 @@ def main():
 
     # ---- the one cluster: single GPU (N = 1), or node-sharded across the N ranks ----
     single = None
-    if world == 1 or not sharded_head or rank == 0:
-        # N = 1 headline; with N > 1 rank 0's single-GPU run is the sharded run's parity reference
+    if world == 1 or a.shard == "none" or (a.full and (not sharded_head or rank == 0)):
+        # N = 1 headline; with N > 1 (--full) rank 0's single-GPU run is the sharded run's parity reference
         single = single_cluster(a, D if (world == 1 or not sharded_head) else Local, cl, preds, prios, mode, local)
     D.barrier()
     head = single
@@ -447,7 +502,7 @@ def main():
         sharded = node_sharded(a, D, cl, preds, prios)
         head = sharded
     replicas = None
-    if world > 1 and a.shard != "none" and a.shard != "replicas":
+    if a.full and world > 1 and a.shard != "none" and a.shard != "replicas":
         # side line: each rank its own cluster under its own LeastRequested weight (weak scaling)
         prios_r = [(k, w + rank) if k == "LeastRequestedPriority" else (k, w) for k, w in prios]
         r_args = argparse.Namespace(**vars(a))
@@ -483,6 +538,10 @@ def main():
             print(json.dumps(line))
             D.close()
             return
+        if a.dump_outputs:
+            # the last timed ksim_schedule call's node index per pod (-1 = FitError); reasons are not collected
+            final = head.get("merged", head["out"])
+            dump_outputs(a.dump_outputs, {"placements": final[len(final) - head["last"]:]})
         pods_timed = head["pods"]
         elapsed = head["elapsed"]
         value = (world if (world > 1 and a.shard == "replicas") else 1) * pods_timed / elapsed
@@ -677,7 +736,6 @@ def main_c5(a):
     --sweep-pods pods of the queue on its own copy of the snapshot (strong scaling: the total
     scenario count is fixed).  value = scenario-pods scheduled by all ranks per second."""
     import numpy as np
-    import torch
     from ksim import scheduler, synth
 
     if a.sweep_form == "scan":
@@ -702,6 +760,9 @@ def main_c5(a):
     tree = st.mode == 3  # KSIM_MODE_TREE: one tree-mode wave per scenario (ksim_tree.hip)
     barrier_sync()
     elapsed = D.allmax(time.perf_counter() - t0)
+    if rank == 0 and a.dump_outputs:
+        # the last timed ksim_sweep call: rank 0's scenarios x pods node indices and final counters
+        dump_outputs(a.dump_outputs, {"placements": out, "counters": ctr})
     n = cl.n_nodes
     scen_pods = len(scen) * a.sweep_pods * a.steps
     value = scen_pods / elapsed

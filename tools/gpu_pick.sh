@@ -18,7 +18,7 @@ tail -2 $OUT/pytest_pick.log
 for w in c2 c2x; do
   for v in serve launch scan; do
     KSIM_SERVE=$([ $v = serve ] && echo 1 || echo 0) KSIM_NO_PICK=$([ $v = scan ] && echo 1 || echo 0) KSIM_SERVE_STATS=1 \
-      timeout -k 10 300 python3 bench.py --workload $w --cpu-sample 0 --steps 2 --warmup 1 > $OUT/bench_${w}_$v.json 2> $OUT/bench_${w}_$v.err || { tail $OUT/bench_${w}_$v.err; exit 1; }
+      timeout -k 10 300 python3 bench.py --full --workload $w --cpu-sample 0 --steps 2 --warmup 1 > $OUT/bench_${w}_$v.json 2> $OUT/bench_${w}_$v.err || { tail $OUT/bench_${w}_$v.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open('$OUT/bench_${w}_$v.json')); p=d.get('per_pod') or {}; print('$w $v', [(m['cached_pods'], m['us_per_call'], m['p99_us'], m['adapter_pattern']['us_per_pod'], m['adapter_pattern']['p99_us']) for m in p.get('marks', [])])"
     grep "ksim serve" $OUT/bench_${w}_$v.err | tail -2 || true
   done

@@ -16,14 +16,14 @@ if [ "$WHAT" = suite ]; then
   tail -1 $OUT/smoke.log
   exit 0
 fi
-timeout -k 10 300 python3 bench.py > $OUT/bench_c3.json 2> $OUT/bench_c3.err || { echo "bench failed"; tail $OUT/bench_c3.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_c3.json 2> $OUT/bench_c3.err || { echo "bench failed"; tail $OUT/bench_c3.err; exit 1; }
 cut -c1-300 $OUT/bench_c3.json
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c3 -o run -- python3 bench.py > $OUT/bench_c3_under_rocprof.json 2> $OUT/prof_c3.err || { echo "rocprof failed"; tail $OUT/prof_c3.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c3 -o run -- python3 bench.py --full > $OUT/bench_c3_under_rocprof.json 2> $OUT/prof_c3.err || { echo "rocprof failed"; tail $OUT/prof_c3.err; exit 1; }
 for w in c2 c2x; do
-  timeout -k 10 300 python3 bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { echo "bench $w failed"; tail $OUT/bench_$w.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { echo "bench $w failed"; tail $OUT/bench_$w.err; exit 1; }
   cut -c1-200 $OUT/bench_$w.json
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2x -o run -- python3 bench.py --workload c2x --cpu-sample 0 > $OUT/bench_c2x_under_rocprof.json 2> $OUT/prof_c2x.err || { echo "rocprof c2x failed"; tail $OUT/prof_c2x.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2x -o run -- python3 bench.py --full --workload c2x --cpu-sample 0 > $OUT/bench_c2x_under_rocprof.json 2> $OUT/prof_c2x.err || { echo "rocprof c2x failed"; tail $OUT/prof_c2x.err; exit 1; }
 for w in c3 c2 c2x; do
   mkdir -p $OUT/pmc_$w
   for ctr in FETCH_SIZE WRITE_SIZE; do
