@@ -12,13 +12,11 @@
 // the device-side pod cursor.  Launches are replayed from a hipGraph, so per-pod host
 // work is zero and no PCIe traffic happens between pods.
 #include "ksim_common.h"
+#include "ksim_decide.h"
 #include "ksim_wave.h"
+#include "ksim_xchg.h"
 
 namespace {
-
-// wave reductions on the DPP helpers (row shifts / broadcasts, no LDS permute)
-__device__ __forceinline__ int64_t wave_max_i64(int64_t v) { return ksimw::max_i64(v); }
-__device__ __forceinline__ int32_t wave_sum_i32(int32_t v) { return ksimw::sum_i32(v); }
 
 // inclusive prefix sum over the 256-thread block (4 waves)
 __device__ __forceinline__ int64_t block_incl_scan(int64_t v, int64_t* s_w) {
@@ -34,14 +32,6 @@ __device__ __forceinline__ int64_t block_incl_scan(int64_t v, int64_t* s_w) {
   for (int k = 0; k < wv; ++k) add += s_w[k];
   __syncthreads();
   return v + add;
-}
-
-// cross-device exchange words (fine-grained buffers written by peers over xGMI)
-__device__ __forceinline__ void lx_store(uint64_t* g, uint64_t v) {
-  __hip_atomic_store(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ uint64_t lx_load(const uint64_t* g) {
-  return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 struct Decision {
@@ -348,7 +338,7 @@ __device__ __forceinline__ bool passa_reduce(const KsimCtx& c, int64_t pod, bool
                             : (int64_t)__hip_atomic_load(&A.asum[lane - A0 - 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         px[me * KSIM_PX_REC + lane] = v;
         for (int r = 0; r < c.sh_world; ++r)
-          lx_store(c.sh_peers[r] + (int64_t)KSIM_LX_SLOTS * KSIM_MAX_RANKS * KSIM_LX_REC +
+          ksimx::store_system(c.sh_peers[r] + (int64_t)KSIM_LX_SLOTS * KSIM_MAX_RANKS * KSIM_LX_REC +
                        ((int64_t)slot * KSIM_MAX_RANKS + me) * KSIM_PX_REC + lane,
                    tag | ((uint64_t)(v + KSIM_LX_BIAS) & vmask));
       }
@@ -359,7 +349,7 @@ __device__ __forceinline__ bool passa_reduce(const KsimCtx& c, int64_t pod, bool
         for (int x = lane; x < c.sh_world * W; x += 64) {
           const int r = x / W, j = x % W;
           if (r == me) continue;
-          const uint64_t v = lx_load(base0 + ((int64_t)slot * KSIM_MAX_RANKS + r) * KSIM_PX_REC + j);
+          const uint64_t v = ksimx::load_system(base0 + ((int64_t)slot * KSIM_MAX_RANKS + r) * KSIM_PX_REC + j);
           if ((v & ~vmask) != tag) { ready = false; continue; }
           px[r * KSIM_PX_REC + j] = (int64_t)(v & vmask) - KSIM_LX_BIAS;
         }
@@ -386,8 +376,8 @@ __device__ __forceinline__ bool passa_reduce(const KsimCtx& c, int64_t pod, bool
           A.asum[lane - A0 - 3] = 0;
         }
       }
-      const int64_t zm = wave_max_i64(lane >= 4 && lane < A0 ? g : 0);
-      const int64_t am = wave_max_i64(lane >= A0 + 3 && lane < W ? g : 0);
+      const int64_t zm = ksimw::max_i64(lane >= 4 && lane < A0 ? g : 0);
+      const int64_t am = ksimw::max_i64(lane >= A0 + 3 && lane < W ? g : 0);
       r0 = __shfl(g, 0, 64); r1 = __shfl(g, 1, 64); r2 = __shfl(g, 2, 64); r3 = __shfl(g, 3, 64);
       const int64_t g5 = __shfl(g, A0 & 63, 64), g6 = __shfl(g, (A0 + 1) & 63, 64), g7 = __shfl(g, (A0 + 2) & 63, 64);
       if (lane == 0) {
@@ -541,7 +531,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
   __shared__ uint32_t s_gen;
   __shared__ int s_bail;
   __shared__ uint64_t s_ctr;
-  __shared__ int64_t s_Mq[KSIM_MAX_RCLASS], s_tot[KSIM_MAX_RCLASS];
+  __shared__ int64_t s_Mq[KSIM_MAX_RCLASS];
   __shared__ int32_t s_Cq[KSIM_MAX_RCLASS];
   __shared__ int64_t s_tv[KSIM_MAX_WIDE], s_av[KSIM_MAX_WIDE], s_ad[KSIM_MAX_WIDE];
   // wide pods (K > KSIM_MAX_RCLASS): per class the block's max and count, then the grid's, and the
@@ -734,7 +724,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
 #pragma unroll
     for (int k = 0; k < NPT; ++k)
       if (fit[k] && cl[k] == q && sc[k] > v) v = sc[k];
-    const int64_t wm = wave_max_i64(v);
+    const int64_t wm = ksimw::max_i64(v);
     int32_t n = 0;
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
@@ -773,11 +763,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
     for (int q = 0; q < (wide ? 0 : K); ++q) {
       int64_t m = INT64_MIN;
       int32_t n = 0;
-      for (int w = 0; w < KSIM_WAVES; ++w) {
-        if (s_cnt[w][q] == 0) continue;
-        if (s_mx[w][q] > m) { m = s_mx[w][q]; n = s_cnt[w][q]; }
-        else if (s_mx[w][q] == m) n += s_cnt[w][q];
-      }
+      for (int w = 0; w < KSIM_WAVES; ++w) ksim_fold_max(m, n, s_mx[w][q], s_cnt[w][q]);
       p->mx[q] = m;
       p->cnt[q] = n;
     }
@@ -829,13 +815,13 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
       else if (m == lm[q]) ln[q] += n;
     }
   }
-  const int32_t wf = wave_sum_i32(lf);
+  const int32_t wf = ksimw::sum_i32(lf);
   if (lane == 0) s_fit[wv] = wf;
 #pragma unroll
   for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
     if (q >= K || wide) break;
-    const int64_t wm = wave_max_i64(ln[q] ? lm[q] : INT64_MIN);
-    const int32_t wn = wave_sum_i32((ln[q] && lm[q] == wm) ? ln[q] : 0);
+    const int64_t wm = ksimw::max_i64(ln[q] ? lm[q] : INT64_MIN);
+    const int32_t wn = ksimw::sum_i32((ln[q] && lm[q] == wm) ? ln[q] : 0);
     if (lane == 0) { s_mx[wv][q] = wm; s_cnt[wv][q] = wn; }
   }
   __syncthreads();
@@ -851,11 +837,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
       for (int q = 0; q < K; ++q) {
         int64_t m = INT64_MIN;
         int32_t n = 0;
-        for (int w = 0; w < KSIM_WAVES; ++w) {
-          if (s_cnt[w][q] == 0) continue;
-          if (s_mx[w][q] > m) { m = s_mx[w][q]; n = s_cnt[w][q]; }
-          else if (s_mx[w][q] == m) n += s_cnt[w][q];
-        }
+        for (int w = 0; w < KSIM_WAVES; ++w) ksim_fold_max(m, n, s_mx[w][q], s_cnt[w][q]);
         s_rM[me][q] = m;
         s_rC[me][q] = n;
       }
@@ -874,7 +856,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
       };
       for (int x = lane; x < c.sh_world * W; x += 64) {
         const int r = x / W, j = x % W;
-        lx_store(c.sh_peers[r] + ((int64_t)slot * KSIM_MAX_RANKS + me) * KSIM_LX_REC + j, tag | word(j));
+        ksimx::store_system(c.sh_peers[r] + ((int64_t)slot * KSIM_MAX_RANKS + me) * KSIM_LX_REC + j, tag | word(j));
       }
       const uint64_t* mine = c.sh_peers[me] + (int64_t)slot * KSIM_MAX_RANKS * KSIM_LX_REC;
       const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
@@ -884,7 +866,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
         for (int x = lane; x < c.sh_world * W; x += 64) {
           const int r = x / W, j = x % W;
           if (r == me) continue;
-          const uint64_t v = lx_load(mine + (int64_t)r * KSIM_LX_REC + j);
+          const uint64_t v = ksimx::load_system(mine + (int64_t)r * KSIM_LX_REC + j);
           if ((v & ~vmask) != tag) { ready = false; continue; }
           const uint64_t val = v & vmask;
           if (j == 0) s_rF[r] = (int32_t)val;
@@ -913,11 +895,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
       for (int q = 0; q < K; ++q) {
         int64_t m = INT64_MIN;
         int32_t n = 0;
-        for (int r = 0; r < c.sh_world; ++r) {
-          if (s_rC[r][q] == 0) continue;
-          if (s_rM[r][q] > m) { m = s_rM[r][q]; n = s_rC[r][q]; }
-          else if (s_rM[r][q] == m) n += s_rC[r][q];
-        }
+        for (int r = 0; r < c.sh_world; ++r) ksim_fold_max(m, n, s_rM[r][q], s_rC[r][q]);
         s_mx[0][q] = m;
         s_cnt[0][q] = n;
         for (int w = 1; w < KSIM_WAVES; ++w) s_cnt[w][q] = 0;
@@ -935,10 +913,8 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
       int32_t n = 0;
       for (int b = 0; b < G; ++b) {
         const int32_t cb = c.wcnt[(int64_t)b * KSIM_MAX_WIDE + q];
-        if (!cb) continue;
-        const int64_t mb = c.wmx[(int64_t)b * KSIM_MAX_WIDE + q];
-        if (mb > m) { m = mb; n = cb; }
-        else if (mb == m) n += cb;
+        if (!cb) continue;  // (its max is not read)
+        ksim_fold_max(m, n, c.wmx[(int64_t)b * KSIM_MAX_WIDE + q], cb);
       }
       s_wm[q] = m;
       s_wc[q] = n;
@@ -947,8 +923,8 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
         if (k2 > 1 || c.w[KSIM_W_NODE_AFFINITY]) mA = s_av[q] > mA ? s_av[q] : mA;
       }
     }
-    mT = wave_max_i64(mT);
-    mA = wave_max_i64(mA);
+    mT = ksimw::max_i64(mT);
+    mA = ksimw::max_i64(mA);
     if (lane == 0) { s_v[0][wv] = mT; s_v[1][wv] = mA; }
     __syncthreads();
     mT = 0; mA = 0;
@@ -958,13 +934,10 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
     }
     for (int q = tid; q < K; q += KSIM_BLOCK) {
       if (!s_wc[q]) continue;
-      uint64_t t = (uint64_t)s_wm[q];
-      if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(s_tv[q], mT, true);
-      if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(s_av[q], mA, false);
-      t += (uint64_t)s_ad[q];
-      tq = (int64_t)t > tq ? (int64_t)t : tq;
+      const int64_t t = ksim_class_total(c, s_wm[q], s_tv[q], s_av[q], s_ad[q], mT, mA);
+      tq = t > tq ? t : tq;
     }
-    const int64_t best_w = wave_max_i64(tq);
+    const int64_t best_w = ksimw::max_i64(tq);
     __syncthreads();  // s_v reused
     if (lane == 0) s_v[0][wv] = best_w;
     __syncthreads();
@@ -972,19 +945,12 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
     for (int w = 0; w < KSIM_WAVES; ++w) best = s_v[0][w] > best ? s_v[0][w] : best;
     int64_t cw = 0;
     for (int q = tid; q < K; q += KSIM_BLOCK) {
-      bool win = false;
-      if (s_wc[q]) {
-        uint64_t t = (uint64_t)s_wm[q];
-        if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(s_tv[q], mT, true);
-        if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(s_av[q], mA, false);
-        t += (uint64_t)s_ad[q];
-        win = (int64_t)t == best;
-      }
+      const bool win = s_wc[q] && ksim_class_total(c, s_wm[q], s_tv[q], s_av[q], s_ad[q], mT, mA) == best;
       s_ww[q] = win ? 1 : 0;
       if (win) cw += s_wc[q];
     }
     __syncthreads();  // s_v reused
-    const int32_t cws = wave_sum_i32((int32_t)cw);
+    const int32_t cws = ksimw::sum_i32((int32_t)cw);
     if (lane == 0) s_cnt[wv][0] = cws;
     __syncthreads();
   }
@@ -999,83 +965,49 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
     D.node = -1;
     D.blk = -1;
     D.rank = 0;
+    auto select = [&](int64_t C) {  // selectHost's index among C nodes; the counter moves on
+      const uint64_t li = s_ctr;
+      D.ix = ksim_select_ix(li, (uint32_t)C);
+      *c.counter = li + 1;
+      s_ctr = li + 1;
+    };
     if (F == 0) {
       D.mode = 0;
     } else if (F == 1) {  // generic_scheduler.go:153-156: no selectHost, no counter bump
       D.mode = 1;
       D.ix = 0;
     } else if (wide) {  // the winners and their count from the wide combine above
+      // (three branches that each end in select(), not one: folding the one-class and wide cases into
+      // the general one, or sharing the tail, costs ksim_scan_kernel<2, true> a wave of occupancy)
       D.mode = 2;
       int64_t C = 0;
       for (int w = 0; w < KSIM_WAVES; ++w) C += s_cnt[w][0];
       D.winners = 0;
-      const uint64_t li = s_ctr;  // generic_scheduler.go:192-195
-      D.ix = ((li >> 32) == 0 && C < ((int64_t)1 << 32)) ? (int64_t)((uint32_t)li % (uint32_t)C) : (int64_t)(li % (uint64_t)C);
-      *c.counter = li + 1;
-      s_ctr = li + 1;
+      select(C);
     } else if (K == 1) {  // one reduce class: it wins, its count at the maximum is C
       D.mode = 2;
       int64_t m = INT64_MIN;
       int32_t n = 0;
-      for (int w = 0; w < KSIM_WAVES; ++w) {
-        const int32_t cw = s_cnt[w][0];
-        const int64_t mw = s_mx[w][0];
-        if (cw == 0) continue;
-        if (mw > m) { m = mw; n = cw; }
-        else if (mw == m) n += cw;
-      }
+      for (int w = 0; w < KSIM_WAVES; ++w) ksim_fold_max(m, n, s_mx[w][0], s_cnt[w][0]);
       D.winners = 1u;
       D.M[0] = m;
-      const uint64_t li = s_ctr;  // generic_scheduler.go:192-195
-      const int64_t C = n;
-      D.ix = ((li >> 32) == 0 && C < ((int64_t)1 << 32)) ? (int64_t)((uint32_t)li % (uint32_t)C) : (int64_t)(li % (uint64_t)C);
-      *c.counter = li + 1;
-      s_ctr = li + 1;
+      select(n);
     } else {
       D.mode = 2;
-      int64_t* const Mq = s_Mq;  // per-class arrays in LDS: private arrays indexed by a run-time
-      int32_t* const Cq = s_Cq;  // class would live in scratch memory
-      int64_t* const tot = s_tot;
+      // per-class arrays in LDS: private arrays indexed by a run-time class would live in scratch memory
       for (int q = 0; q < K; ++q) {
         int64_t m = INT64_MIN;
         int32_t n = 0;
-        for (int w = 0; w < KSIM_WAVES; ++w) {
-          if (s_cnt[w][q] == 0) continue;
-          if (s_mx[w][q] > m) { m = s_mx[w][q]; n = s_cnt[w][q]; }
-          else if (s_mx[w][q] == m) n += s_cnt[w][q];
-        }
-        Mq[q] = m;
-        Cq[q] = n;
+        for (int w = 0; w < KSIM_WAVES; ++w) ksim_fold_max(m, n, s_mx[w][q], s_cnt[w][q]);
+        s_Mq[q] = m;
+        s_Cq[q] = n;
       }
-      // reduce priorities over the filtered set (NormalizeReduce)
-      int64_t mxT = 0, mxA = 0;
-      for (int q = 0; q < K; ++q) {
-        if (Cq[q] == 0) continue;
-        const int64_t tv = s_tv[q];
-        const int64_t av = s_av[q];
-        if (k1 > 1 || c.w[KSIM_W_TAINT_TOLERATION]) mxT = tv > mxT ? tv : mxT;
-        if (k2 > 1 || c.w[KSIM_W_NODE_AFFINITY]) mxA = av > mxA ? av : mxA;
-      }
-      int64_t best = INT64_MIN;
-      for (int q = 0; q < K; ++q) {
-        if (Cq[q] == 0) continue;
-        uint64_t t = (uint64_t)Mq[q];
-        if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(s_tv[q], mxT, true);
-        if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(s_av[q], mxA, false);
-        t += (uint64_t)s_ad[q];  // NodePreferAvoidPods (0 without the addends)
-        tot[q] = (int64_t)t;
-        if (tot[q] > best) best = tot[q];
-      }
-      uint32_t win = 0;
-      int64_t C = 0;
-      for (int q = 0; q < K; ++q)
-        if (Cq[q] && tot[q] == best) { win |= 1u << q; C += Cq[q]; }
+      uint32_t win;
+      int64_t best;
+      const int64_t C = ksim_decide_serial<false>(c, K, k1, k2, s_Mq, s_Cq, s_tv, s_av, s_ad, win, best);
       D.winners = win;
-      for (int q = 0; q < K; ++q) D.M[q] = Mq[q];
-      const uint64_t li = s_ctr;                // generic_scheduler.go:192-195
-      D.ix = ((li >> 32) == 0 && C < ((int64_t)1 << 32)) ? (int64_t)((uint32_t)li % (uint32_t)C) : (int64_t)(li % (uint64_t)C);
-      *c.counter = li + 1;
-      s_ctr = li + 1;
+      for (int q = 0; q < K; ++q) D.M[q] = s_Mq[q];
+      select(C);
     }
   }
   __syncthreads();
@@ -1111,7 +1043,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_scan_kernel(KsimCtx c) {
       for (int r = 0; r < KSIM_NREASONS; ++r) {
         int32_t v = 0;
         for (int b = tid; b < G; b += KSIM_BLOCK) v += c.partials[b].hist[r];
-        v = wave_sum_i32(v);
+        v = ksimw::sum_i32(v);
         if (lane == 0) s_cnt[wv][0] = v;
         __syncthreads();
         if (tid == 0) c.out_reasons[pod * KSIM_NREASONS + r] = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
@@ -1414,7 +1346,7 @@ __global__ __launch_bounds__(ONE_BLOCK) void ksim_one_kernel(KsimCtx c) {
 #pragma unroll
     for (int k = 0; k < NPT; ++k)
       if (fit[k] && cl[k] == q && sc[k] > v) v = sc[k];
-    const int64_t wm = wave_max_i64(v);
+    const int64_t wm = ksimw::max_i64(v);
     int32_t n = 0;
 #pragma unroll
     for (int k = 0; k < NPT; ++k) n += __popcll(__ballot(fit[k] && cl[k] == q && sc[k] == wm));
@@ -1460,46 +1392,18 @@ __global__ __launch_bounds__(ONE_BLOCK) void ksim_one_kernel(KsimCtx c) {
         int64_t m = INT64_MIN;
         int32_t n = 0;
         if (q < K)
-          for (int w = 0; w < ONE_WAVES; ++w) {
-            const int32_t cw = s_cnt[w][q];
-            const int64_t mw = s_mx[w][q];
-            if (cw == 0) continue;
-            if (mw > m) { m = mw; n = cw; }
-            else if (mw == m) n += cw;
-          }
+          for (int w = 0; w < ONE_WAVES; ++w) ksim_fold_max(m, n, s_mx[w][q], s_cnt[w][q]);
         Mq[q] = m;
         Cq[q] = n;
       }
-      // reduce priorities over the filtered set (NormalizeReduce), as ksim_scan_kernel
-      int64_t mxT = 0, mxA = 0;
-#pragma unroll
-      for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-        if (q >= K || Cq[q] == 0) continue;
-        if (k1 > 1 || c.w[KSIM_W_TAINT_TOLERATION]) mxT = s_tv[q] > mxT ? s_tv[q] : mxT;
-        if (k2 > 1 || c.w[KSIM_W_NODE_AFFINITY]) mxA = s_av[q] > mxA ? s_av[q] : mxA;
-      }
-      int64_t best = INT64_MIN, tot[KSIM_MAX_RCLASS];
-#pragma unroll
-      for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-        tot[q] = INT64_MIN;
-        if (q >= K || Cq[q] == 0) continue;
-        uint64_t t = (uint64_t)Mq[q];
-        if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(s_tv[q], mxT, true);
-        if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(s_av[q], mxA, false);
-        t += (uint64_t)s_ad[q];  // NodePreferAvoidPods
-        tot[q] = (int64_t)t;
-        best = tot[q] > best ? tot[q] : best;
-      }
-      uint32_t win = 0;
-      int64_t C = 0;
-#pragma unroll
-      for (int q = 0; q < KSIM_MAX_RCLASS; ++q)
-        if (q < K && Cq[q] && tot[q] == best) { win |= 1u << q; C += Cq[q]; }
+      uint32_t win;
+      int64_t best;
+      const int64_t C = ksim_decide_serial<true>(c, K, k1, k2, Mq, Cq, s_tv, s_av, s_ad, win, best);
       D.winners = win;
 #pragma unroll
       for (int q = 0; q < KSIM_MAX_RCLASS; ++q) D.M[q] = Mq[q];
-      const uint64_t li = pre_ctr;  // generic_scheduler.go:192-195
-      D.ix = ((li >> 32) == 0 && C < ((int64_t)1 << 32)) ? (int64_t)((uint32_t)li % (uint32_t)C) : (int64_t)(li % (uint64_t)C);
+      const uint64_t li = pre_ctr;
+      D.ix = ksim_select_ix(li, (uint32_t)C);
       pre_ctr = li + 1;
       *c.counter = pre_ctr;
     }
@@ -1599,12 +1503,6 @@ __device__ __forceinline__ uint64_t pk_enc(uint32_t tag, int64_t v) {
 }
 __device__ __forceinline__ int64_t pk_dec(uint64_t w) { return ((int64_t)(w << 8)) >> 8; }
 __device__ __forceinline__ uint32_t pk_tag(uint64_t w) { return (uint32_t)(w >> 56); }
-__device__ __forceinline__ void pk_store(uint64_t* g, uint64_t v) {
-  __hip_atomic_store(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t pk_load(const uint64_t* g) {
-  return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 constexpr uint64_t PK_SPIN_TICKS = 200000000ull;  // 2 s of s_memrealtime
 constexpr int PK_BATCH = 16;  // record words one lane keeps in flight (a cross-XCD load is ~1 µs)
 // The resident form's answer (ksim_serve_kernel; KsimServeBox::ans in host memory): lane k of the
@@ -1816,7 +1714,7 @@ __device__ __forceinline__ void ksim_pick_body(const KsimCtx& c, const ksim_pod&
         v = (int64_t)s_az[lane - A0 - 3];
       }
       // every word of the record, not only the W read now: see the record stores below
-      pk_store(recA + (int64_t)me * KSIM_PICK_RA + lane, pk_enc(tag, lane < W ? v : 0));
+      ksimx::store_agent(recA + (int64_t)me * KSIM_PICK_RA + lane, pk_enc(tag, lane < W ? v : 0));
     }
     if (wv == 0) {
       // every block's record: lane x combines word x over the blocks
@@ -1829,7 +1727,7 @@ __device__ __forceinline__ void ksim_pick_body(const KsimCtx& c, const ksim_pod&
           uint64_t wd[PK_BATCH];  // one batch of blocks' words in flight: one round trip per batch
 #pragma unroll
           for (int j = 0; j < PK_BATCH; ++j)
-            wd[j] = b0 + j < G ? pk_load(recA + (int64_t)(b0 + j) * KSIM_PICK_RA + lane) : pk_enc(tag, 0);
+            wd[j] = b0 + j < G ? ksimx::load_agent(recA + (int64_t)(b0 + j) * KSIM_PICK_RA + lane) : pk_enc(tag, 0);
 #pragma unroll
           for (int j = 0; j < PK_BATCH; ++j) {
             if (b0 + j >= G) break;
@@ -1946,11 +1844,11 @@ __device__ __forceinline__ void ksim_pick_body(const KsimCtx& c, const ksim_pod&
       else if (lane <= K) v = cq ? mq : 0;  // (a class without fit nodes: count 0, max unread)
       else if (lane <= 2 * K) v = cq2;
       else if (lane < WB) v = s_hist[lane - 1 - 2 * K];
-      if (!pass_a) pk_store(recA + (int64_t)me * KSIM_PICK_RA + lane, pk_enc(tag, 0));
-      pk_store(recB + (int64_t)me * KSIM_PICK_RB + lane, pk_enc(tag, v));
+      if (!pass_a) ksimx::store_agent(recA + (int64_t)me * KSIM_PICK_RA + lane, pk_enc(tag, 0));
+      ksimx::store_agent(recB + (int64_t)me * KSIM_PICK_RB + lane, pk_enc(tag, v));
       // word 64 (the last reason when K = 16) from lane 0
       static_assert(KSIM_PICK_RB == 65 && KSIM_PICK_RA == 64, "record words per lane");
-      if (lane == 0) pk_store(recB + (int64_t)me * KSIM_PICK_RB + 64, pk_enc(tag, 64 < WB ? s_hist[64 - 1 - 2 * K] : 0));
+      if (lane == 0) ksimx::store_agent(recB + (int64_t)me * KSIM_PICK_RB + 64, pk_enc(tag, 64 < WB ? s_hist[64 - 1 - 2 * K] : 0));
     }
   }
   if (wv == 0) {
@@ -1965,7 +1863,7 @@ __device__ __forceinline__ void ksim_pick_body(const KsimCtx& c, const ksim_pod&
           uint64_t w[PK_BATCH];  // one batch of words in flight: one round trip per batch
 #pragma unroll
           for (int j = 0; j < PK_BATCH; ++j)
-            w[j] = x0 + j <= 2 * K ? pk_load(recB + (int64_t)lane * KSIM_PICK_RB + x0 + j) : pk_enc(tag, 0);
+            w[j] = x0 + j <= 2 * K ? ksimx::load_agent(recB + (int64_t)lane * KSIM_PICK_RB + x0 + j) : pk_enc(tag, 0);
 #pragma unroll
           for (int j = 0; j < PK_BATCH; ++j) {
             if (x0 + j > 2 * K) break;
@@ -1993,29 +1891,18 @@ __device__ __forceinline__ void ksim_pick_body(const KsimCtx& c, const ksim_pod&
         if (lane == 0) { s_M[q] = m; s_C[q] = n; }
       }
       PKST(6);
-      // reduce priorities over the filtered set (NormalizeReduce), as ksim_scan_kernel, lane q =
-      // class q: the maxima over the live classes and the winners by wave reductions
+      // lane q = class q: NormalizeReduce over the live classes, the totals and the winners
       const bool live = lane < K && s_C[lane] > 0;
-      const int64_t tvq = lane < K ? s_tv[lane] : 0, avq = lane < K ? s_av[lane] : 0;
-      const int64_t mxT = ksimw::max_i64(live && (k1 > 1 || c.w[KSIM_W_TAINT_TOLERATION]) ? tvq : 0);
-      const int64_t mxA = ksimw::max_i64(live && (k2 > 1 || c.w[KSIM_W_NODE_AFFINITY]) ? avq : 0);
-      int64_t tot = INT64_MIN;
-      if (live) {
-        uint64_t t = (uint64_t)s_M[lane];
-        if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(tvq, mxT, true);
-        if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(avq, mxA, false);
-        t += (uint64_t)s_ad[lane];  // NodePreferAvoidPods
-        tot = (int64_t)t;
-      }
-      const int64_t best = ksimw::max_i64(tot);
-      const bool w_q = live && tot == best;
-      win = (uint32_t)__ballot(w_q);
-      C = ksimw::sum_i32(w_q ? s_C[lane] : 0);
+      uint64_t wb;
+      int64_t best;
+      C = ksim_decide_lanes<KsimReduceWave>(c, live, live ? s_M[lane] : 0, live ? s_C[lane] : 0, lane < K ? s_tv[lane] : 0,
+                                            lane < K ? s_av[lane] : 0, lane < K ? s_ad[lane] : 0, wb, best);
+      win = (uint32_t)wb;
     }
     // selectHost: the ix-th match counted from the largest name rank down (blocks from the top)
     const uint64_t li = s_ctr;
     int64_t ix = 0;
-    if (mode == 2) ix = ((li >> 32) == 0 && C < ((int64_t)1 << 32)) ? (int64_t)((uint32_t)li % (uint32_t)C) : (int64_t)(li % (uint64_t)C);
+    if (mode == 2) ix = ksim_select_ix(li, (uint32_t)C);
     int64_t mt = 0;  // this lane's block: its matches
     if (in && mode == 1) mt = fb;
     if (in && mode == 2)
@@ -2071,7 +1958,7 @@ __device__ __forceinline__ void ksim_pick_body(const KsimCtx& c, const ksim_pod&
           uint64_t wd[PK_BATCH];  // one batch of blocks' words in flight
 #pragma unroll
           for (int j = 0; j < PK_BATCH; ++j)
-            wd[j] = b0 + j < G ? pk_load(recB + (int64_t)(b0 + j) * KSIM_PICK_RB + 1 + 2 * K + lane) : pk_enc(tag, 0);
+            wd[j] = b0 + j < G ? ksimx::load_agent(recB + (int64_t)(b0 + j) * KSIM_PICK_RB + 1 + 2 * K + lane) : pk_enc(tag, 0);
 #pragma unroll
           for (int j = 0; j < PK_BATCH; ++j) {
             if (b0 + j >= G) break;
@@ -2248,10 +2135,6 @@ __device__ uint32_t serve_veto(uint64_t* st, uint32_t ep) {
       return 1;
   }
 }
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(v >> 32)) << 32) |
-         (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
-}
 }  // namespace
 
 template <int NPT, bool AUX>
@@ -2344,7 +2227,7 @@ __global__ __launch_bounds__(KSIM_BLOCK) void ksim_serve_kernel(KsimCtx c, KsimS
           // the vote stands until every block voted (LEFT) or a block saw a message (new epoch)
           uint64_t sv = 0;
           if (lane == 0) sv = __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          sv = rfl64(sv);
+          sv = ksimx::rfl64(sv);
           if (sv & KSIM_SERVE_ST_LEFT) break;
           if (KSIM_SERVE_ST_EPOCH(sv) != vote_ep) { voted = false; t_idle = now; }
         } else if (now - t_idle > a.idle_ticks) {

@@ -34,8 +34,10 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "ksim_decide.h"
 #include "ksim_fast.h"
 #include "ksim_wave.h"
+#include "ksim_xchg.h"
 
 namespace {
 
@@ -48,14 +50,12 @@ constexpr int NSLOT = 4;                             // granule slots (pod mod N
 constexpr int MAXG = 64 * MAXB;                      // workgroups a slot is sized for
 constexpr int KF = 4;                                // reduce classes polled per round trip
 
-typedef __attribute__((address_space(1))) uint64_t gu64;
+using ksimx::gu64;  // the granule exchange goes through global (not flat) accesses
+using ksimx::gtag;
+using ksimx::gfit;
+using ksimx::gcnt;
+using ksimx::gscore;
 
-__device__ __forceinline__ void store_granule(uint64_t* g, uint64_t v) {
-  __hip_atomic_store((gu64*)g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t load_granule(const uint64_t* g) {
-  return __hip_atomic_load((gu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // speculative partial of workgroup b for the pod in `slot`, and the previous owner's correction
 // Dense layout [slot][q][pos(b)]: one poll of class 0 touches 2 KiB (16 lines) instead of a
 // line per workgroup.  pos(b) = (b % MAXB) * 64 + b / MAXB, so the sweep's j-th load of lane l
@@ -72,10 +72,6 @@ template <int MB>
 __device__ __forceinline__ uint64_t* gran_at(uint64_t* gr, int slot, int b, int q, int X) {
   return b == X ? fix_at(gr, slot, q) : spec_at<MB>(gr, slot, b, q);
 }
-__device__ __forceinline__ uint32_t gtag(uint64_t v) { return (uint32_t)(v >> 56); }
-__device__ __forceinline__ int32_t gfit(uint64_t v) { return (int32_t)((v >> 44) & 0xFFF); }
-__device__ __forceinline__ int32_t gcnt(uint64_t v) { return (int32_t)((v >> 32) & 0xFFF); }
-__device__ __forceinline__ int32_t gscore(uint64_t v) { return (int32_t)(uint32_t)v; }
 
 // critical-path probe (diagnostic builds, -DKSIM_PROBE=k): a 512-cycle delay at point k; the
 // per-pod time grows by the delay only where k sits on the critical path
@@ -214,34 +210,22 @@ __device__ __noinline__ void commit_ports_lds(const KsimCtx* __restrict__ cg, co
   c.port_count[w] = cnt;
 }
 
-// Total score of reduce class q once the per-class maxima over the filtered set are known
-// (NormalizeReduce, priorities/reduce.go:29-64; weighted sum generic_scheduler.go:632-639).
-// tv / av: the class's TaintToleration / NodeAffinity map values (prefetched per pod).
-__device__ __forceinline__ int64_t class_total(const KsimCtx& c, int64_t tv, int64_t av, int64_t ad, int64_t base,
-                                               int64_t mxT, int64_t mxA) {
-  uint64_t t = (uint64_t)base + (uint64_t)ad;  // ad: NodePreferAvoidPods' weighted score of the class
-  if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(tv, mxT, true);
-  if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(av, mxA, false);
-  return (int64_t)t;
-}
-
-// wave-wide maximum of a 64-bit value: the DPP int32 reduction when every lane's value fits
-// (the common case: counts, weights, scores), else a shuffle tree (ds_bpermute, ~10x slower)
-__device__ __forceinline__ int64_t wave_max_i64(int64_t v) {
-  if (__all(v >= INT32_MIN && v <= INT32_MAX)) return ksimw::max_i32((int32_t)v);
+// The decision's wave reductions (ksim_decide_lanes).  The maximum of a 64-bit value: the DPP int32
+// reduction when every lane's value fits (the common case: counts, weights, scores), else a
+// shuffle tree (ds_bpermute, ~10x slower).  NONE fits too: totals are >= 0.
+struct ReduceFast32 {
+  static constexpr int64_t NONE = -1;
+  static __device__ __forceinline__ int64_t max(int64_t v) {
+    if (__all(v >= INT32_MIN && v <= INT32_MAX)) return ksimw::max_i32((int32_t)v);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int64_t t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
+    for (int o = 32; o > 0; o >>= 1) {
+      const int64_t t = __shfl_xor(v, o, 64);
+      v = t > v ? t : v;
+    }
+    return v;
   }
-  return v;
-}
-
-// 64-bit value of lane q (wave-uniform q)
-__device__ __forceinline__ int64_t readlane64(int64_t v, int q) {
-  return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)((uint64_t)v >> 32), q) << 32) |
-                   (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)v, q));
-}
+  static __device__ __forceinline__ int32_t sum(int32_t v) { return ksimw::sum_i32(v); }
+};
 
 // A committed pod's change to a row (NodeInfo.AddPod of the resource-only part): the dual
 // hypothesis evaluates the next pod on row + delta.  pp: the two pods' host ports conflict.
@@ -789,7 +773,7 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
       if (lane == 0) s_arr[buf] = 0;
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       const uint64_t v = combine(K, buf);
-      if (lane < K) store_granule(spec_at<MB>(granules, (int)(p % NSLOT), blockIdx.x, lane), (ptag(p) << 56) | v);
+      if (lane < K) ksimx::store_agent((gu64*)spec_at<MB>(granules, (int)(p % NSLOT), blockIdx.x, lane), (ptag(p) << 56) | v);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       if (lane == 0) __hip_atomic_store(&s_done[buf], (int32_t)ptag(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -852,8 +836,8 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
         // unconditional loads (slots are sized for MAXG workgroups): one fabric round trip for
         // class 0, the owner's correction and (KF at a time) the further reduce classes
 #pragma unroll
-        for (int j = 0; j < MB; ++j) g[j] = load_granule(spec_at<MB>(granules, slot, lane * MB + j, 0));
-        const uint64_t fx = load_granule(fix_at(granules, slot, 0));
+        for (int j = 0; j < MB; ++j) g[j] = ksimx::load_agent((gu64*)spec_at<MB>(granules, slot, lane * MB + j, 0));
+        const uint64_t fx = ksimx::load_agent((gu64*)fix_at(granules, slot, 0));
         bool mine = X < 0 || gtag(fx) == tag;
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
@@ -867,7 +851,7 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
               const int b = lane * MB + j;
-              v[u][j] = (q0 + u < K && b < G) ? load_granule(gran_at<MB>(granules, slot, b, q0 + u, X)) : 0;
+              v[u][j] = (q0 + u < K && b < G) ? ksimx::load_agent((gu64*)gran_at<MB>(granules, slot, b, q0 + u, X)) : 0;
             }
 #pragma unroll
           for (int u = 0; u < KF; ++u)
@@ -910,10 +894,7 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
 #pragma unroll
         for (int j = 0; j < MB; ++j) {
           f += gfit(g[j]);
-          const int32_t cnt = gcnt(g[j]), s = gscore(g[j]);
-          if (cnt == 0) continue;
-          if (s > m) { m = s; n = cnt; }
-          else if (s == m) n += cnt;
+          ksim_fold_max(m, n, gscore(g[j]), gcnt(g[j]));
         }
         F = ksimw::sum_i32(f);
         M0 = ksimw::max_i32(n ? m : -1);
@@ -929,10 +910,7 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
 #pragma unroll
           for (int j = 0; j < MB; ++j) {
             const int b = lane * MB + j;
-            const int32_t cnt = b < G ? gcnt(v[j]) : 0, s = gscore(v[j]);
-            if (cnt == 0) continue;
-            if (s > mm) { mm = s; nn = cnt; }
-            else if (s == mm) nn += cnt;
+            ksim_fold_max(mm, nn, gscore(v[j]), b < G ? gcnt(v[j]) : 0);
           }
           const int32_t Mq = ksimw::max_i32(nn ? mm : -1);
           const int32_t Cq = ksimw::sum_i32((nn && mm == Mq) ? nn : 0);
@@ -967,19 +945,15 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
             // set (classes with fit nodes), each class's weighted total, the best total and the
             // classes that reach it (reduce.go:29-64, generic_scheduler.go:632-639)
             const bool live = lane < K && cq_l != 0;
-            const int32_t cq = live ? cq_l : 0;
-            const int64_t mq = live ? mq_l : 0;
-            const int64_t mxT = wave_max_i64(live ? tv_l : 0), mxA = wave_max_i64(live ? av_l : 0);
-            const int64_t t = live ? class_total(c, tv_l, av_l, ad_l, mq, mxT, mxA) : -1;  // totals are >= 0
-            const int64_t best = wave_max_i64(t);
-            const uint64_t wbm = __ballot(live && t == best);
+            uint64_t wbm;
+            int64_t best;
+            C = ksim_decide_lanes<ReduceFast32>(c, live, live ? mq_l : 0, cq_l, tv_l, av_l, ad_l, wbm, best);
             win = (uint32_t)wbm;
-            C = ksimw::sum_i32((wbm >> lane) & 1ull ? cq : 0);
-            tgt = ((wbm >> lane) & 1ull) ? ((lane << EV_SHIFT) | (int32_t)mq) : -2;
+            tgt = ((wbm >> lane) & 1ull) ? ((lane << EV_SHIFT) | mq_l) : -2;
           } else {
             tgt = lane == 0 ? M0 : -2;
           }
-          ix = (counter >> 32) ? (int64_t)(counter % (uint64_t)C) : (int64_t)((uint32_t)counter % (uint32_t)C);
+          ix = ksim_select_ix(counter, (uint32_t)C);
           counter += 1;  // generic_scheduler.go:192-195
         }
         STAMP(10);
@@ -1060,7 +1034,7 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
 #pragma unroll
           for (int w = NW - 1; w >= 1; --w) {  // rows of wave w: (w-1)*64 + lane; the top first
             if (jsel >= 0) break;
-            const uint64_t m = (uint64_t)readlane64((int64_t)cm, w);
+            const uint64_t m = (uint64_t)ksimw::readlane64((int64_t)cm, w);
             const int nbits = __popcll(m);
             if (rr >= nbits) { rr -= nbits; continue; }
             const bool is = ((m >> lane) & 1ull) && __popcll((m >> lane) >> 1) == rr;
@@ -1174,7 +1148,7 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
             }
             if (n == 0) m = -1;
             const uint64_t v = (lane == 0 ? ((uint64_t)f << 44) : 0) | ((uint64_t)n << 32) | (uint64_t)(uint32_t)m;
-            if (lane < Kn) store_granule(fix_at(granules, (int)((pod + 1) % NSLOT), lane), (ptag(pod + 1) << 56) | v);
+            if (lane < Kn) ksimx::store_agent((gu64*)fix_at(granules, (int)((pod + 1) % NSLOT), lane), (ptag(pod + 1) << 56) | v);
             OSTAMP(19);
             PROBE(4);
             if (dual) {
@@ -1329,12 +1303,68 @@ __global__ __launch_bounds__(BS) void ksim_persistent_kernel(KsimCtx c, const Ks
 }
 
 // Checks the DPP wave helpers against plain lane loops (diagnostic, tests/ only).
-__global__ void ksim_wave_selftest_kernel(int32_t* out) {
-  const int lane = threadIdx.x;
-  const int32_t v = (int32_t)((lane * 7919 + 13) % 97) - 40 + (blockIdx.x * 11);
-  out[(blockIdx.x * 3 + 0) * 64 + lane] = ksimw::max_i32(v);
-  out[(blockIdx.x * 3 + 1) * 64 + lane] = ksimw::sum_i32(v);
-  out[(blockIdx.x * 3 + 2) * 64 + lane] = ksimw::prefix_incl_i32(v);
+__device__ __host__ inline int32_t st_v32(int b, int l) { return (int32_t)((l * 7919 + 13) % 97) - 40 + (b * 11); }
+__device__ __host__ inline int64_t st_v64(int b, int l) { return (int64_t)st_v32(b, l) * 4294967311ll + l; }
+__device__ __host__ inline int st_src(int b) { return (b * 17 + 5) % 64; }  // readlane64's source lane
+
+__global__ void ksim_wave_selftest_kernel(int32_t* out, int64_t* out64) {
+  const int lane = threadIdx.x, b = blockIdx.x;
+  const int32_t v = st_v32(b, lane);
+  out[(b * 3 + 0) * 64 + lane] = ksimw::max_i32(v);
+  out[(b * 3 + 1) * 64 + lane] = ksimw::sum_i32(v);
+  out[(b * 3 + 2) * 64 + lane] = ksimw::prefix_incl_i32(v);
+  const int64_t w = st_v64(b, lane);
+  out64[(b * 6 + 0) * 64 + lane] = ksimw::max_i64(w);
+  out64[(b * 6 + 1) * 64 + lane] = ksimw::min_i64(w);
+  out64[(b * 6 + 2) * 64 + lane] = ksimw::sum_i64(w);
+  out64[(b * 6 + 3) * 64 + lane] = ksimw::max16_i64(w);
+  out64[(b * 6 + 4) * 64 + lane] = ksimw::sum16_i32(v);
+  out64[(b * 6 + 5) * 64 + lane] = ksimw::readlane64(w, st_src(b));
+}
+
+// One case of the decision (ksim_decide.h) and what each form of it answers.
+struct DecideCase {
+  int32_t K, k1, k2, wset;
+  uint64_t lni;  // lastNodeIndex
+  int64_t M[KSIM_MAX_RCLASS], tv[KSIM_MAX_RCLASS], av[KSIM_MAX_RCLASS], ad[KSIM_MAX_RCLASS];
+  int32_t Cn[KSIM_MAX_RCLASS];
+};
+struct DecideOut {
+  int64_t win, C, ix, best;
+};
+constexpr int DECIDE_FORMS = 5;  // lanes over the wave / one DPP row / int32 fast path, serial unrolled / looped
+
+// Block b runs case b when the launch's weights (c.w) are the case's.
+__global__ __launch_bounds__(64) void ksim_decide_selftest_kernel(KsimCtx c, int wset, const DecideCase* cases, DecideOut* out) {
+  const DecideCase& cs = cases[blockIdx.x];
+  if (cs.wset != wset) return;
+  const int lane = threadIdx.x, K = cs.K;
+  DecideOut* o = out + blockIdx.x * DECIDE_FORMS;
+  const bool in = lane < K;
+  const int32_t Cq = in ? cs.Cn[lane] : 0;
+  const int64_t Mq = in ? cs.M[lane] : 0, tv = in ? cs.tv[lane] : 0, av = in ? cs.av[lane] : 0, ad = in ? cs.ad[lane] : 0;
+  auto put = [&](int f, uint64_t win, int64_t C, int64_t best) {
+    if (lane == 0) o[f] = DecideOut{(int64_t)win, C, C > 0 ? ksim_select_ix(cs.lni, (uint32_t)C) : -1, best};
+  };
+  uint64_t wb;
+  int64_t best;
+  int64_t C = ksim_decide_lanes<KsimReduceWave>(c, Cq > 0, Mq, Cq, tv, av, ad, wb, best);
+  put(0, wb, C, best);
+  C = ksim_decide_lanes<KsimReduceRow16>(c, Cq > 0, Mq, Cq, tv, av, ad, wb, best);
+  put(1, wb, C, best);
+  C = ksim_decide_lanes<ReduceFast32>(c, Cq > 0, Mq, Cq, tv, av, ad, wb, best);
+  put(2, wb, C, best);
+  if (lane == 0) {
+    int64_t m[KSIM_MAX_RCLASS];
+    int32_t n[KSIM_MAX_RCLASS];
+#pragma unroll
+    for (int q = 0; q < KSIM_MAX_RCLASS; ++q) { m[q] = cs.M[q]; n[q] = cs.Cn[q]; }
+    uint32_t win;
+    C = ksim_decide_serial<true>(c, K, cs.k1, cs.k2, m, n, cs.tv, cs.av, cs.ad, win, best);
+    put(3, win, C, best);
+    C = ksim_decide_serial<false>(c, K, cs.k1, cs.k2, cs.M, cs.Cn, cs.tv, cs.av, cs.ad, win, best);
+    put(4, win, C, best);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1432,30 +1462,145 @@ extern "C" hipError_t ksim_launch_persistent(const KsimCtx* c, const KsimCtx* cd
   return launch_persistent<512, 8, MAXB>(c, cdev, granules, grid, lds_rows, s);
 }
 
+// The fixed table of decision cases: K in {1, 2, 5, 16}; classes without nodes; all-zero class
+// values (mx == 0) for either term; a zero weight with k1 > 1; class values >= 2^20 and >= 2^40
+// (ksim_norm's three branches); ties at the best total; counters around 2^32 and 2^64.
+static constexpr int DECIDE_CASES = 40;
+static const int64_t DECIDE_W[4][2] = {{1, 1}, {0, 1}, {2, 3}, {1, 0}};  // TaintToleration, NodeAffinity weights
+
+static DecideCase decide_case(int i) {
+  static const int Ks[4] = {1, 2, 5, 16}, k2s[4] = {1, 2, 5, 4};
+  static const uint64_t ctrs[5] = {0, 0xFFFFFFFFull, 1ull << 32, (1ull << 32) + 5, ~0ull};
+  static const int32_t c1[3] = {1, 3, 7};
+  DecideCase d{};
+  d.K = Ks[i % 4]; d.k2 = k2s[i % 4]; d.k1 = d.K / d.k2;
+  d.wset = (i / 4) % 4;
+  d.lni = ctrs[i % 5];
+  const bool tie = i % 10 == 9;  // every class alike: all the live ones reach the best total
+  for (int q = 0; q < d.K; ++q) {
+    const int x = tie ? 0 : q;
+    int64_t tv = (x * 5 + i) % 7, av = (x * 3 + i) % 5;
+    if (i % 8 == 5) tv = (tv + 1) << 20;
+    if (i % 8 == 6) tv = (tv + 1) << 40;
+    if (i % 8 == 2) av = (av + 1) << 20;
+    if (i % 8 == 3) av = (av + 1) << 40;
+    if (i % 8 == 1) tv = 0;
+    if (i % 8 == 4 || i % 16 == 7) av = 0;
+    d.tv[q] = tv; d.av[q] = av;
+    d.M[q] = (x * 11 + i * 7) % 23;
+    d.ad[q] = i % 3 == 0 ? (x % 3) * 5 : 0;
+    d.Cn[q] = (q * 3 + i) % 4;  // 0: a class without fit nodes
+  }
+  if (d.K == 1) d.Cn[0] = c1[(i / 4) % 3];
+  else d.Cn[i % d.K] = 1 + i % 3;
+  return d;
+}
+
+// NormalizeReduce with plain truncating division (reduce.go:29-64)
+static int64_t decide_norm_ref(int64_t v, int64_t mx, bool reverse) {
+  if (mx == 0) return reverse ? 10 : v;
+  const int64_t s = 10 * v / mx;
+  return reverse ? 10 - s : s;
+}
+
+static DecideOut decide_ref(const DecideCase& d) {
+  const int64_t wT = DECIDE_W[d.wset][0], wA = DECIDE_W[d.wset][1];
+  int64_t mxT = 0, mxA = 0;
+  for (int q = 0; q < d.K; ++q) {
+    if (!d.Cn[q]) continue;
+    mxT = d.tv[q] > mxT ? d.tv[q] : mxT;
+    mxA = d.av[q] > mxA ? d.av[q] : mxA;
+  }
+  DecideOut r{0, 0, -1, INT64_MIN};
+  int64_t tot[KSIM_MAX_RCLASS];
+  for (int q = 0; q < d.K; ++q) {
+    if (!d.Cn[q]) continue;
+    tot[q] = d.M[q] + d.ad[q] + wT * decide_norm_ref(d.tv[q], mxT, true) + wA * decide_norm_ref(d.av[q], mxA, false);
+    r.best = tot[q] > r.best ? tot[q] : r.best;
+  }
+  for (int q = 0; q < d.K; ++q)
+    if (d.Cn[q] && tot[q] == r.best) { r.win |= (int64_t)1 << q; r.C += d.Cn[q]; }
+  r.ix = (int64_t)(d.lni % (uint64_t)r.C);
+  return r;
+}
+
+static int decide_selftest() {
+  DecideCase hc[DECIDE_CASES];
+  for (int i = 0; i < DECIDE_CASES; ++i) hc[i] = decide_case(i);
+  DecideCase* dc = nullptr;
+  DecideOut* dout = nullptr;
+  DecideOut ho[DECIDE_CASES * DECIDE_FORMS];
+  int bad = -1;
+  if (hipMalloc(&dc, sizeof hc) == hipSuccess && hipMalloc(&dout, sizeof ho) == hipSuccess &&
+      hipMemcpy(dc, hc, sizeof hc, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dout, 0xFF, sizeof ho) == hipSuccess) {
+    for (int ws = 0; ws < 4; ++ws) {
+      KsimCtx c{};
+      c.w[KSIM_W_TAINT_TOLERATION] = DECIDE_W[ws][0];
+      c.w[KSIM_W_NODE_AFFINITY] = DECIDE_W[ws][1];
+      hipLaunchKernelGGL(ksim_decide_selftest_kernel, dim3(DECIDE_CASES), dim3(64), 0, 0, c, ws, dc, dout);
+    }
+    if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(ho, dout, sizeof ho, hipMemcpyDeviceToHost) == hipSuccess) {
+      bad = 0;
+      int ties = 0, dead = 0;
+      for (int i = 0; i < DECIDE_CASES; ++i) {
+        const DecideOut r = decide_ref(hc[i]);
+        ties += (r.win & (r.win - 1)) != 0;
+        for (int q = 0; q < hc[i].K; ++q) dead += hc[i].Cn[q] == 0;
+        for (int f = 0; f < DECIDE_FORMS; ++f) {
+          const DecideOut& g = ho[i * DECIDE_FORMS + f];
+          bad += g.win != r.win || g.C != r.C || g.ix != r.ix || g.best != r.best;
+        }
+      }
+      bad += ties == 0 || dead == 0;  // the table lost a case it is there for
+    }
+  }
+  (void)hipFree(dc);
+  (void)hipFree(dout);
+  return bad;
+}
+
 extern "C" int ksim_selftest(void) {
   int32_t* d = nullptr;
   const int nb = 4;
+  int64_t* d64 = nullptr;
   if (hipMalloc(&d, nb * 3 * 64 * sizeof(int32_t)) != hipSuccess) return -1;
-  hipLaunchKernelGGL(ksim_wave_selftest_kernel, dim3(nb), dim3(64), 0, 0, d);
+  if (hipMalloc(&d64, nb * 6 * 64 * sizeof(int64_t)) != hipSuccess) { (void)hipFree(d); return -1; }
+  hipLaunchKernelGGL(ksim_wave_selftest_kernel, dim3(nb), dim3(64), 0, 0, d, d64);
   int32_t h[nb * 3 * 64];
+  int64_t h64[nb * 6 * 64];
   int bad = -1;
-  if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+  if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess &&
+      hipMemcpy(h64, d64, sizeof h64, hipMemcpyDeviceToHost) == hipSuccess) {
     bad = 0;
     for (int b = 0; b < nb; ++b) {
-      int32_t v[64], mx = INT32_MIN, sum = 0, pre = 0;
+      int32_t v[64], mx = INT32_MIN, sum = 0, pre = 0, sum16 = 0;
+      int64_t mx64 = INT64_MIN, mn64 = INT64_MAX, sum64 = 0, mx16 = INT64_MIN;
       for (int l = 0; l < 64; ++l) {
-        v[l] = (int32_t)((l * 7919 + 13) % 97) - 40 + b * 11;
+        v[l] = st_v32(b, l);
         mx = v[l] > mx ? v[l] : mx;
         sum += v[l];
+        const int64_t w = st_v64(b, l);
+        mx64 = w > mx64 ? w : mx64;
+        mn64 = w < mn64 ? w : mn64;
+        sum64 += w;
+        if (l < 16) { mx16 = w > mx16 ? w : mx16; sum16 += v[l]; }
       }
       for (int l = 0; l < 64; ++l) {
         pre += v[l];
         bad += h[(b * 3 + 0) * 64 + l] != mx;
         bad += h[(b * 3 + 1) * 64 + l] != sum;
         bad += h[(b * 3 + 2) * 64 + l] != pre;
+        bad += h64[(b * 6 + 0) * 64 + l] != mx64;
+        bad += h64[(b * 6 + 1) * 64 + l] != mn64;
+        bad += h64[(b * 6 + 2) * 64 + l] != sum64;
+        bad += h64[(b * 6 + 3) * 64 + l] != mx16;
+        bad += h64[(b * 6 + 4) * 64 + l] != sum16;
+        bad += h64[(b * 6 + 5) * 64 + l] != st_v64(b, st_src(b));
       }
     }
   }
   (void)hipFree(d);
+  (void)hipFree(d64);
+  if (bad == 0) bad = decide_selftest();
   return bad;
 }

@@ -29,10 +29,12 @@
 //    workgroup holding the ix-th match from the top (core/generic_scheduler.go:183-198).
 #include <algorithm>
 
+#include "ksim_decide.h"
 #include "ksim_f64.h"
 #include "ksim_fast.h"
 #include "ksim_tree.h"
 #include "ksim_wave.h"
+#include "ksim_xchg.h"
 
 using namespace kf64;
 
@@ -54,22 +56,7 @@ constexpr int RING_FILL = 8;    // descriptors fetched per refill
 constexpr uint64_t SPIN_LIMIT_TICKS = 200000000ull;  // s_memrealtime at 100 MHz = 2 s
 constexpr int ANSLOT = 8;       // aggregate slots per rank (pod mod ANSLOT)
 
-typedef __attribute__((address_space(1))) uint64_t gu64;
-
-// cross-device exchange (fine-grained memory written by peers over xGMI)
-__device__ __forceinline__ void sys_store(uint64_t* g, uint64_t v) {
-  __hip_atomic_store(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ uint64_t sys_load(const uint64_t* g) {
-  return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__device__ __forceinline__ void store_granule(uint64_t* g, uint64_t v) {
-  __hip_atomic_store((gu64*)g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t load_granule(const uint64_t* g) {
-  return __hip_atomic_load((gu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+using ksimx::gu64;  // the granule exchange goes through global (not flat) accesses
 // [slot][pos(b)], pos(b) = (b % MAXB) * 64 + b / MAXB: the sweep's j-th load of lane l is
 // workgroup l*MAXB + j and each load instruction is 512 contiguous bytes.
 __device__ __forceinline__ uint64_t* spec_at(uint64_t* gr, int slot, int b) {
@@ -420,10 +407,10 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       if (t.m2 < 0) t.c2 = 0;
       if (lane == 0) {
         s_wg[buf][0] = t.f; s_wg[buf][1] = t.m1; s_wg[buf][2] = t.c1; s_wg[buf][3] = t.m2; s_wg[buf][4] = t.c2;
-        if (NR == 1) store_granule(spec_at(granules, (int)(p % NSLOT), me), gpack(ptag(p), t.f, t.c1, t.m1));
+        if (NR == 1) ksimx::store_agent((gu64*)spec_at(granules, (int)(p % NSLOT), me), gpack(ptag(p), t.f, t.c1, t.m1));
       }
       if (NR > 1 && lane < NR)
-        store_granule(spec_at(granules + lane * REP_STRIDE, (int)(p % NSLOT), me), gpack(ptag(p), t.f, t.c1, t.m1));
+        ksimx::store_agent((gu64*)spec_at(granules + lane * REP_STRIDE, (int)(p % NSLOT), me), gpack(ptag(p), t.f, t.c1, t.m1));
     }
   };
   // LDS form, control wave: the 64-row segments holding rows at the workgroup maximum of the pod in `buf`
@@ -549,8 +536,8 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
       for (;;) {
 #pragma unroll
-        for (int j = 0; j < MAXB; ++j) g[j] = load_granule(my_rep + slot * MAXG + j * 64 + lane);
-        fx = load_granule(fix_at(my_rep, slot));
+        for (int j = 0; j < MAXB; ++j) g[j] = ksimx::load_agent((gu64*)my_rep + slot * MAXG + j * 64 + lane);
+        fx = ksimx::load_agent((gu64*)fix_at(my_rep, slot));
         bool mine = X < 0 || gtag(fx) == tag;
 #pragma unroll
         for (int j = 0; j < MAXB; ++j) {
@@ -599,18 +586,18 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         const int aslot = (int)(pod % ANSLOT);
         if (me == 0 && lane < a.world) {
           uint64_t* dst = a.peers[lane] + ((int64_t)aslot * KSIM_MAX_RANKS + a.rank) * 4;
-          sys_store(dst, at | (uint32_t)Fl);
-          sys_store(dst + 1, at | (stop_any ? 0x80000000ull : 0ull) | (uint32_t)Cl);
-          sys_store(dst + 2, at | (uint32_t)Ml);
+          ksimx::store_system(dst, at | (uint32_t)Fl);
+          ksimx::store_system(dst + 1, at | (stop_any ? 0x80000000ull : 0ull) | (uint32_t)Cl);
+          ksimx::store_system(dst + 2, at | (uint32_t)Ml);
         }
         const bool rl = lane < a.world;
         const uint64_t* src = a.xchg + ((int64_t)aslot * KSIM_MAX_RANKS + (rl ? lane : 0)) * 4;
         uint64_t w0 = 0, w1 = 0, w2 = 0;
         const uint64_t hi = 0xFFFFFFFF00000000ull;
         for (;;) {
-          w0 = sys_load(src);
-          w1 = sys_load(src + 1);
-          w2 = sys_load(src + 2);
+          w0 = ksimx::load_system(src);
+          w1 = ksimx::load_system(src + 1);
+          w2 = ksimx::load_system(src + 2);
           if (__all(!rl || ((w0 & hi) == at && (w1 & hi) == at && (w2 & hi) == at))) break;
           // the first pod of a call doubles as the start handshake: the peers' kernels may start late
           const uint64_t lim = (pod == a.first) ? a.start_ticks : SPIN_LIMIT_TICKS;
@@ -628,7 +615,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         stop_any = __any(rl && ((w1 >> 31) & 1));
       }
       const uint32_t Cs = C ? C : 1u;
-      const int64_t ix = (counter >> 32) ? (int64_t)(counter % (uint64_t)Cs) : (int64_t)((uint32_t)counter % Cs);
+      const int64_t ix = ksim_select_ix(counter, Cs);
       const int64_t ixl = ix - above_r;  // index among this rank's matches, from the top
       const int64_t above = (int64_t)Cl - pre;  // matches in workgroups of higher lanes
       const bool hit = Ml == M0 && tot > 0 && ixl >= above && ixl < above + tot;
@@ -861,11 +848,11 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           const int32_t Ff = f0 - (rem ? 1 : 0) + (add ? 1 : 0);
           PROBE(2);
           if (NR > 1 && lane < NR)
-            store_granule(fix_at(granules + lane * REP_STRIDE, (int)((pod + 1) % NSLOT)),
+            ksimx::store_agent((gu64*)fix_at(granules + lane * REP_STRIDE, (int)((pod + 1) % NSLOT)),
                           gpack(ptag(pod + 1), Ff, Cn, Cn ? M : -1) | stopbit);
           if (lane == 0) {
             if (NR == 1)
-              store_granule(fix_at(granules, (int)((pod + 1) % NSLOT)), gpack(ptag(pod + 1), Ff, Cn, Cn ? M : -1) | stopbit);
+              ksimx::store_agent((gu64*)fix_at(granules, (int)((pod + 1) % NSLOT)), gpack(ptag(pod + 1), Ff, Cn, Cn ? M : -1) | stopbit);
             s_wg[nb][0] = Ff; s_wg[nb][1] = Cn ? M : -1; s_wg[nb][2] = Cn;
           }
         }

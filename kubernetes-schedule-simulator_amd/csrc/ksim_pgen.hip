@@ -39,8 +39,10 @@
 // bounded (2 s → error bit 4).
 #include <algorithm>
 
+#include "ksim_decide.h"
 #include "ksim_pgen.h"
 #include "ksim_wave.h"
+#include "ksim_xchg.h"
 
 #define PG_BS 256
 #define PG_NW (PG_BS / 64)
@@ -68,22 +70,17 @@ namespace {
 constexpr uint64_t M56 = (1ull << 56) - 1;
 constexpr int64_t B55 = (int64_t)1 << 55;
 
-__device__ __forceinline__ void pg_store(uint64_t* p, uint64_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t pg_load(const uint64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+using ksimx::gtag;
+using ksimx::gfit;
+using ksimx::gcnt;
+using ksimx::gscore;
+using ksimx::rfl64;
 __device__ __forceinline__ uint64_t* rec_at(uint64_t* g, int slot, int word, int b) {
   return g + ((int64_t)slot * PG_RA + word) * PG_MAXG + b;
 }
 __device__ __forceinline__ uint64_t* cls_at(uint64_t* g, int slot, int q, int b) {
   return g + (int64_t)PG_NSLOT * PG_RA * PG_MAXG + ((int64_t)slot * KSIM_MAX_RCLASS + q) * PG_MAXG + b;
 }
-__device__ __forceinline__ uint32_t gtag(uint64_t v) { return (uint32_t)(v >> 56); }
-__device__ __forceinline__ int32_t gfit(uint64_t v) { return (int32_t)((v >> 44) & 0xFFF); }
-__device__ __forceinline__ int32_t gcnt(uint64_t v) { return (int32_t)((v >> 32) & 0xFFF); }
-__device__ __forceinline__ int32_t gscore(uint64_t v) { return (int32_t)(uint32_t)v; }
 
 // The workgroup's LDS image (ksim_pgen_plan's layout).
 struct PgL {
@@ -124,11 +121,6 @@ struct PgX {
 // The pod's uniform fields, read once from its LDS record into scalar registers (the evaluation's
 // branches on them are then scalar, and no LDS round trip sits in front of them).
 __device__ __forceinline__ int32_t rfl(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t rfl64(int64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 __device__ __forceinline__ PgHdr pg_hdr_u(const PgHdr& x) {
   PgHdr h;
   h.K = rfl(x.K); h.k1 = rfl(x.k1); h.k2 = rfl(x.k2); h.sp = rfl(x.sp); h.fl = rfl(x.fl);
@@ -592,6 +584,217 @@ __device__ __forceinline__ void pg_write_back(const KsimCtx& c, const PGenArgs& 
   } while (0)
 #endif
 
+namespace {
+
+// Wave 0 publishes the workgroup's class granules of the pod: lane q folds the waves' partials of
+// class q into tag | fit count (class 0 only) | count at max | max score.
+template <int NW>
+__device__ __forceinline__ void pg_publish_classes(const PGenArgs& g, int K, int slot, uint32_t tag, int lane,
+                                                   const int32_t (&s_fit)[NW], const int32_t (&s_mx)[NW][KSIM_MAX_RCLASS],
+                                                   const int32_t (&s_cn)[NW][KSIM_MAX_RCLASS]) {
+  if (lane >= K) return;
+  int32_t m = -1, nn = 0, f = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    f += s_fit[w];
+    ksim_fold_max(m, nn, s_mx[w][lane], s_cn[w][lane]);
+  }
+  const uint64_t v = ((uint64_t)tag << 56) | (lane == 0 ? ((uint64_t)f << 44) : 0) | ((uint64_t)nn << 32) |
+                     (uint64_t)(uint32_t)m;
+  ksimx::store_agent(cls_at(g.gran, slot, lane, blockIdx.x), v);
+}
+
+// Step 4 of wave 0, the same in both kernels: sweep every workgroup's class granules of the pod until
+// all carry its tag, decide (ksim_decide.h) and locate the workgroup holding the chosen node.
+// mode: -1 a spin ran out or the counts disagree (err set), 0 no node fits, 1 a single fit, 2
+// selectHost ran (counter advanced); blk / rank: the owning workgroup and the node's rank from its
+// top; win: the winning classes; tgt_l: lane q holds class q's maximum if q wins, else -2.
+// stamp(k): diagnostic phase marks (7: the sweep ended, 11: the per-class maxima are known).
+template <int MB, class Stamp>
+__device__ __forceinline__ void pg_sweep_decide(const KsimCtx& c, const PGenArgs& g, const PgX& X, int K, int k2, int G,
+                                                int slot, uint32_t tag, int lane, uint64_t& counter, int& mode,
+                                                int& blk, int& rank, uint32_t& win, int32_t& tgt_l, Stamp stamp) {
+  mode = 0; blk = -1; rank = 0; win = 0; tgt_l = -2;
+  // the decision's per-class map values (lane q = reduce class q)
+  int64_t tv_l = 0, av_l = 0, ad_l = 0;
+  if (lane < K) {
+    tv_l = X.tv(K > 1 ? lane / k2 : 0);
+    av_l = X.av(K > 1 ? lane % k2 : 0);
+    ad_l = X.ad(K > 1 ? lane % k2 : 0);
+  }
+  // the workgroup holding the ix-th match from the top (lane-major workgroup order: lane l
+  // holds l, l + 64, ...; name rank grows with the workgroup index), bm = matches per workgroup
+  auto locate = [&](const int32_t (&bm)[MB], int64_t ix) {
+    // matches in workgroups above b = (lanes above, same m) + (every lane, higher m)
+    int64_t above = 0;
+    int found = -1, rk = 0;
+#pragma unroll
+    for (int m = MB - 1; m >= 0; --m) {
+    if (found < 0 && 64 * m < G) {
+      const int32_t pre = ksimw::prefix_incl_i32(bm[m]);
+      const int32_t tot = __builtin_amdgcn_readlane(pre, 63);
+      const int64_t ab = above + (int64_t)(tot - pre);
+      const bool hit = bm[m] > 0 && ix >= ab && ix < ab + bm[m];
+      const uint64_t hb = __ballot(hit);
+      if (hb) {
+        const int src = __builtin_ffsll((long long)hb) - 1;
+        found = src + 64 * m;
+        rk = (int)__builtin_amdgcn_readlane((int32_t)(ix - ab), src);
+      }
+      above += tot;
+    }
+    }
+    if (found < 0) { mode = -1; if (lane == 0) atomicOr(c.err, 2); }
+    blk = found;
+    rank = rk;
+  };
+  if (K == 1) {
+    // one reduce class (no TaintToleration / NodeAffinity spread among the fit nodes): the
+    // class maximum is the best total, and only granule 0 of each workgroup is read
+    uint64_t gv0[MB];
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    bool ok = false;
+    for (;;) {
+      bool mine = true;
+#pragma unroll
+      for (int m = 0; m < MB; ++m) {
+        const int b = lane + 64 * m;
+        gv0[m] = b < G ? ksimx::load_agent(cls_at(g.gran, slot, 0, b)) : ((uint64_t)tag << 56);
+        mine &= gtag(gv0[m]) == tag;
+      }
+      if (__all(mine)) { ok = true; break; }
+      if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+  stamp(7);
+    if (!ok) {
+      mode = -1;
+      if (lane == 0) atomicOr(c.err, 4);
+    } else {
+      int32_t f = 0, mm = -1, cc = 0;
+#pragma unroll
+      for (int m = 0; m < MB; ++m) {
+        if (lane + 64 * m >= G) continue;
+        f += gfit(gv0[m]);
+        ksim_fold_max(mm, cc, gscore(gv0[m]), gcnt(gv0[m]));
+      }
+      const int32_t F = ksimw::sum_i32(f);
+      if (F > 0) {
+        mode = 1;
+        int64_t ix = 0;
+        int32_t M0 = -1;
+        if (F > 1) {  // generic_scheduler.go:153-156: a single fit skips selectHost
+          mode = 2;
+          M0 = ksimw::max_i32(cc ? mm : -1);
+          const int32_t C = ksimw::sum_i32((cc && mm == M0) ? cc : 0);
+          win = 1;
+          tgt_l = lane == 0 ? M0 : -2;
+          ix = ksim_select_ix(counter, (uint32_t)C);
+          counter += 1;  // generic_scheduler.go:192-195
+        }
+        int32_t bm[MB];
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+          int32_t sb = 0;
+          if (lane + 64 * m < G)
+            sb = mode == 1 ? gfit(gv0[m]) : ((gcnt(gv0[m]) && gscore(gv0[m]) == M0) ? gcnt(gv0[m]) : 0);
+          bm[m] = sb;
+        }
+        locate(bm, ix);
+      }
+    }
+  } else {
+    uint64_t gv[KSIM_MAX_RCLASS][MB];
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    bool ok = false;
+    for (;;) {
+      bool mine = true;
+#pragma unroll
+      for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+          const int b = lane + 64 * m;
+          gv[q][m] = (q < K && b < G) ? ksimx::load_agent(cls_at(g.gran, slot, q, b)) : ((uint64_t)tag << 56);
+          mine &= gtag(gv[q][m]) == tag;
+        }
+      }
+      if (__all(mine)) { ok = true; break; }
+      if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+  stamp(7);
+    if (!ok) {
+      mode = -1;
+      if (lane == 0) atomicOr(c.err, 4);
+    } else {
+      int32_t F = 0;
+      int32_t mq_l = -1, cq_l = 0;  // lane q: class q's global maximum and its count
+      int32_t f = 0;
+#pragma unroll
+      for (int m = 0; m < MB; ++m) f += (lane + 64 * m < G) ? gfit(gv[0][m]) : 0;
+      F = ksimw::sum_i32(f);
+#pragma unroll
+      for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
+        if (q < K) {
+          int32_t mm = -1, cc = 0;
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {
+            if (lane + 64 * m >= G) continue;
+            ksim_fold_max(mm, cc, gscore(gv[q][m]), gcnt(gv[q][m]));
+          }
+          const int32_t Mq = ksimw::max_i32(cc ? mm : -1);
+          const int32_t Cq = ksimw::sum_i32((cc && mm == Mq) ? cc : 0);
+          mq_l = lane == q ? Mq : mq_l;
+          cq_l = lane == q ? Cq : cq_l;
+        }
+      }
+  stamp(11);
+      if (F > 0) {
+        mode = 1;
+        int64_t ix = 0;
+        if (F > 1) {  // generic_scheduler.go:153-156: a single fit skips selectHost
+          mode = 2;
+          // lane q = reduce class q (K <= 16: the class lanes are one DPP row)
+          const bool live = lane < K && cq_l != 0;
+          uint64_t wbm;
+          int64_t best;
+          const int32_t C = ksim_decide_lanes<KsimReduceRow16>(c, live, mq_l, cq_l, tv_l, av_l, ad_l, wbm, best);
+          win = (uint32_t)wbm;
+          tgt_l = ((wbm >> lane) & 1ull) ? mq_l : -2;
+          ix = ksim_select_ix(counter, (uint32_t)C);
+          counter += 1;  // generic_scheduler.go:192-195
+        }
+        // locate the workgroup holding the ix-th match from the top (lane-major workgroup order:
+        // lane l holds l, l + 64, ...; name rank grows with the workgroup index)
+        int32_t bm[MB];
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+          const int b = lane + 64 * m;
+          int32_t s = 0;
+          if (b < G) {
+            if (mode == 1) {
+              s = gfit(gv[0][m]);
+            } else {
+#pragma unroll
+              for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
+                if (q < K && ((win >> q) & 1u)) {
+                  const int32_t Mq = __builtin_amdgcn_readlane(mq_l, q);
+                  if (gcnt(gv[q][m]) && gscore(gv[q][m]) == Mq) s += gcnt(gv[q][m]);
+                }
+              }
+            }
+          }
+          bm[m] = s;
+        }
+        locate(bm, ix);
+      }
+    }
+  }
+}
+
+
+}  // namespace
+
 // ---- ksim_pgen_pack: one pod-context record per queued pod of [first, end) ----
 __global__ __launch_bounds__(64) void ksim_pgen_pack_kernel(KsimCtx c, PGenArgs g) {
   const int lane = threadIdx.x;
@@ -863,7 +1066,7 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
             v = (int64_t)s_az[lane - A0 - 3];
             s_az[lane - A0 - 3] = 0;
           }
-          pg_store(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | ((uint64_t)(v + B55) & M56));
+          ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | ((uint64_t)(v + B55) & M56));
         }
         // sweep every record: lane l reads workgroups l, l + 64, ...; batches of 8 words
         int64_t a_mn = 0, a_mx = 0, a_smx = 0, a_hz = 0, a_amx = 0, a_atot = 0, a_ahz = 0;
@@ -878,7 +1081,7 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
 #pragma unroll
               for (int m = 0; m < MB; ++m) {
                 const int b = lane + 64 * m;
-                v[u][m] = (w0 + u < RA && b < G) ? pg_load(rec_at(g.gran, slot, w0 + u, b)) : ((uint64_t)tag << 56);
+                v[u][m] = (w0 + u < RA && b < G) ? ksimx::load_agent(rec_at(g.gran, slot, w0 + u, b)) : ((uint64_t)tag << 56);
                 mine &= gtag(v[u][m]) == tag;
               }
             if (__all(mine)) break;
@@ -985,218 +1188,12 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
 
     // ---- 4. wave 0: publish, sweep every workgroup's granules, decide; waves 1-3: prefetch ----
     if (wv == 0) {
-      if (lane < K) {
-        int32_t m = -1, nn = 0, f = 0;
-#pragma unroll
-        for (int w = 0; w < PG_NW; ++w) {
-          f += s_fit[w];
-          if (!s_cn[w][lane]) continue;
-          if (s_mx[w][lane] > m) { m = s_mx[w][lane]; nn = s_cn[w][lane]; }
-          else if (s_mx[w][lane] == m) nn += s_cn[w][lane];
-        }
-        const uint64_t v = ((uint64_t)tag << 56) | (lane == 0 ? ((uint64_t)f << 44) : 0) | ((uint64_t)nn << 32) |
-                           (uint64_t)(uint32_t)m;
-        pg_store(cls_at(g.gran, slot, lane, blockIdx.x), v);
-      }
-      // the decision's per-class map values (lane q = reduce class q)
-      int64_t tv_l = 0, av_l = 0, ad_l = 0;
-      if (lane < K) {
-        tv_l = X.tv(K > 1 ? lane / k2 : 0);
-        av_l = X.av(K > 1 ? lane % k2 : 0);
-        ad_l = X.ad(K > 1 ? lane % k2 : 0);
-      }
-      int mode = 0, blk = -1, rank = 0;
-      uint32_t win = 0;
-      int32_t tgt_l = -2;  // lane q: class q's maximum if q wins
-      // the workgroup holding the ix-th match from the top (lane-major workgroup order: lane l
-      // holds l, l + 64, ...; name rank grows with the workgroup index), bm = matches per workgroup
-      auto locate = [&](const int32_t (&bm)[MB], int64_t ix) {
-        // matches in workgroups above b = (lanes above, same m) + (every lane, higher m)
-        int64_t above = 0;
-        int found = -1, rk = 0;
-#pragma unroll
-        for (int m = MB - 1; m >= 0; --m) {
-        if (found < 0 && 64 * m < G) {
-          const int32_t pre = ksimw::prefix_incl_i32(bm[m]);
-          const int32_t tot = __builtin_amdgcn_readlane(pre, 63);
-          const int64_t ab = above + (int64_t)(tot - pre);
-          const bool hit = bm[m] > 0 && ix >= ab && ix < ab + bm[m];
-          const uint64_t hb = __ballot(hit);
-          if (hb) {
-            const int src = __builtin_ffsll((long long)hb) - 1;
-            found = src + 64 * m;
-            rk = (int)__builtin_amdgcn_readlane((int32_t)(ix - ab), src);
-          }
-          above += tot;
-        }
-        }
-        if (found < 0) { mode = -1; if (lane == 0) atomicOr(c.err, 2); }
-        blk = found;
-        rank = rk;
-      };
-      if (K == 1) {
-        // one reduce class (no TaintToleration / NodeAffinity spread among the fit nodes): the
-        // class maximum is the best total, and only granule 0 of each workgroup is read
-        uint64_t gv0[MB];
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        bool ok = false;
-        for (;;) {
-          bool mine = true;
-#pragma unroll
-          for (int m = 0; m < MB; ++m) {
-            const int b = lane + 64 * m;
-            gv0[m] = b < G ? pg_load(cls_at(g.gran, slot, 0, b)) : ((uint64_t)tag << 56);
-            mine &= gtag(gv0[m]) == tag;
-          }
-          if (__all(mine)) { ok = true; break; }
-          if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-#ifdef KSIM_STAMPS
-        if (blockIdx.x == 0 && tid == 0) PG_STAMP(7);
-#endif
-        if (!ok) {
-          mode = -1;
-          if (lane == 0) atomicOr(c.err, 4);
-        } else {
-          int32_t f = 0, mm = -1, cc = 0;
-#pragma unroll
-          for (int m = 0; m < MB; ++m) {
-            if (lane + 64 * m >= G) continue;
-            f += gfit(gv0[m]);
-            const int32_t cn = gcnt(gv0[m]), sc0 = gscore(gv0[m]);
-            if (!cn) continue;
-            if (sc0 > mm) { mm = sc0; cc = cn; }
-            else if (sc0 == mm) cc += cn;
-          }
-          const int32_t F = ksimw::sum_i32(f);
-          if (F > 0) {
-            mode = 1;
-            int64_t ix = 0;
-            int32_t M0 = -1;
-            if (F > 1) {  // generic_scheduler.go:153-156: a single fit skips selectHost
-              mode = 2;
-              M0 = ksimw::max_i32(cc ? mm : -1);
-              const int32_t C = ksimw::sum_i32((cc && mm == M0) ? cc : 0);
-              win = 1;
-              tgt_l = lane == 0 ? M0 : -2;
-              ix = (counter >> 32) ? (int64_t)(counter % (uint64_t)C) : (int64_t)((uint32_t)counter % (uint32_t)C);
-              counter += 1;  // generic_scheduler.go:192-195
-            }
-            int32_t bm[MB];
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-              int32_t sb = 0;
-              if (lane + 64 * m < G)
-                sb = mode == 1 ? gfit(gv0[m]) : ((gcnt(gv0[m]) && gscore(gv0[m]) == M0) ? gcnt(gv0[m]) : 0);
-              bm[m] = sb;
-            }
-            locate(bm, ix);
-          }
-        }
-      } else {
-        uint64_t gv[KSIM_MAX_RCLASS][MB];
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        bool ok = false;
-        for (;;) {
-          bool mine = true;
-#pragma unroll
-          for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-              const int b = lane + 64 * m;
-              gv[q][m] = (q < K && b < G) ? pg_load(cls_at(g.gran, slot, q, b)) : ((uint64_t)tag << 56);
-              mine &= gtag(gv[q][m]) == tag;
-            }
-          }
-          if (__all(mine)) { ok = true; break; }
-          if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-#ifdef KSIM_STAMPS
-        if (blockIdx.x == 0 && tid == 0) PG_STAMP(7);
-#endif
-        if (!ok) {
-          mode = -1;
-          if (lane == 0) atomicOr(c.err, 4);
-        } else {
-          int32_t F = 0;
-          int32_t mq_l = -1, cq_l = 0;  // lane q: class q's global maximum and its count
-          int32_t f = 0;
-#pragma unroll
-          for (int m = 0; m < MB; ++m) f += (lane + 64 * m < G) ? gfit(gv[0][m]) : 0;
-          F = ksimw::sum_i32(f);
-#pragma unroll
-          for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-            if (q < K) {
-              int32_t mm = -1, cc = 0;
-#pragma unroll
-              for (int m = 0; m < MB; ++m) {
-                if (lane + 64 * m >= G) continue;
-                const int32_t cn = gcnt(gv[q][m]), s = gscore(gv[q][m]);
-                if (!cn) continue;
-                if (s > mm) { mm = s; cc = cn; }
-                else if (s == mm) cc += cn;
-              }
-              const int32_t Mq = ksimw::max_i32(cc ? mm : -1);
-              const int32_t Cq = ksimw::sum_i32((cc && mm == Mq) ? cc : 0);
-              mq_l = lane == q ? Mq : mq_l;
-              cq_l = lane == q ? Cq : cq_l;
-            }
-          }
-#ifdef KSIM_STAMPS
-          if (blockIdx.x == 0 && tid == 0) PG_STAMP(11);
-#endif
-          if (F > 0) {
-            mode = 1;
-            int64_t ix = 0;
-            if (F > 1) {  // generic_scheduler.go:153-156: a single fit skips selectHost
-              mode = 2;
-              // lane q = reduce class q: NormalizeReduce over the filtered set, weighted totals
-              // (reduce.go:29-64, generic_scheduler.go:632-639), the best total and its classes
-              const bool live = lane < K && cq_l != 0;
-              int64_t mxT = 0, mxA = 0;
-              // K <= 16: the class lanes are one DPP row
-              if (k1 > 1 || c.w[KSIM_W_TAINT_TOLERATION]) mxT = ksimw::max16_i64(live ? tv_l : 0);
-              if (k2 > 1 || c.w[KSIM_W_NODE_AFFINITY]) mxA = ksimw::max16_i64(live ? av_l : 0);
-              uint64_t t = (uint64_t)(int64_t)mq_l + (uint64_t)ad_l;
-              if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(tv_l, mxT, true);
-              if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(av_l, mxA, false);
-              const int64_t tot = live ? (int64_t)t : INT64_MIN;
-              const int64_t best = ksimw::max16_i64(tot);
-              const uint64_t wbm = __ballot(live && tot == best);
-              win = (uint32_t)wbm;
-              const int32_t C = ksimw::sum16_i32(((wbm >> lane) & 1ull) ? cq_l : 0);
-              tgt_l = ((wbm >> lane) & 1ull) ? mq_l : -2;
-              ix = (counter >> 32) ? (int64_t)(counter % (uint64_t)C) : (int64_t)((uint32_t)counter % (uint32_t)C);
-              counter += 1;  // generic_scheduler.go:192-195
-            }
-            // locate the workgroup holding the ix-th match from the top (lane-major workgroup order:
-            // lane l holds l, l + 64, ...; name rank grows with the workgroup index)
-            int32_t bm[MB];
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-              const int b = lane + 64 * m;
-              int32_t s = 0;
-              if (b < G) {
-                if (mode == 1) {
-                  s = gfit(gv[0][m]);
-                } else {
-#pragma unroll
-                  for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-                    if (q < K && ((win >> q) & 1u)) {
-                      const int32_t Mq = __builtin_amdgcn_readlane(mq_l, q);
-                      if (gcnt(gv[q][m]) && gscore(gv[q][m]) == Mq) s += gcnt(gv[q][m]);
-                    }
-                  }
-                }
-              }
-              bm[m] = s;
-            }
-            locate(bm, ix);
-          }
-        }
-      }
+      pg_publish_classes<PG_NW>(g, K, slot, tag, lane, s_fit, s_mx, s_cn);
+      int mode, blk, rank;
+      uint32_t win;
+      int32_t tgt_l;
+      pg_sweep_decide<MB>(c, g, X, K, k2, G, slot, tag, lane, counter, mode, blk, rank, win, tgt_l,
+                          [&](int k) { if (blockIdx.x == 0 && tid == 0) PG_STAMP(k); });
 #ifdef KSIM_STAMPS
       if (blockIdx.x == 0 && tid == 0) PG_STAMP(12);
 #endif
@@ -1278,7 +1275,7 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
           pg_svc_commit(g, L, Pr.aff_ident, jsel);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         }
-        pg_store(g.gran + PG_COMMIT_OFF + slot, ((uint64_t)tag << 56) | (uint64_t)w);
+        ksimx::store_agent(g.gran + PG_COMMIT_OFF + slot, ((uint64_t)tag << 56) | (uint64_t)w);
       }
       if (!c.no_commit) {
         // NodeInfo.AddPod on the row (node_info.go:318-341)
@@ -1355,7 +1352,7 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
         // the chosen node, from the owner's commit word
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         uint64_t v;
-        while (gtag(v = pg_load(g.gran + PG_COMMIT_OFF + slot)) != tag) {
+        while (gtag(v = ksimx::load_agent(g.gran + PG_COMMIT_OFF + slot)) != tag) {
           if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) { atomicOr(c.err, 4); s_abort = 1; break; }
           __builtin_amdgcn_s_sleep(1);
         }
@@ -1645,7 +1642,7 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
     const PgHdr H = pg_hdr_u(X.hdr());
     pg_sections(H, X.so);
     const ksim_pod P = pg_pod_u(X.pod());
-    const int K = H.K, k1 = H.k1, k2 = H.k2;
+    const int K = H.K, k2 = H.k2;
     const bool ipa = (H.fl & PGF_IPA) != 0;
     const int32_t sp = H.sp;
     // AUX (an instantiation for handles with the auxiliary priority's tables): the pod may read it
@@ -1716,7 +1713,7 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
             v = (int64_t)s_az[lane - A0 - 3];
             s_az[lane - A0 - 3] = 0;
           }
-          pg_store(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | ((uint64_t)(v + B55) & M56));
+          ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | ((uint64_t)(v + B55) & M56));
         }
 #ifdef KSIM_STAMPS
         t_pub = __builtin_amdgcn_s_memtime();
@@ -1735,7 +1732,7 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
               const int b = (lane & 7) + 8 * m;
-              v[m] = (wl && b < G) ? pg_load(rec_at(g.gran, slot, word, b)) : ((uint64_t)tag << 56);
+              v[m] = (wl && b < G) ? ksimx::load_agent(rec_at(g.gran, slot, word, b)) : ((uint64_t)tag << 56);
               mine &= gtag(v[m]) == tag;
             }
             if (__all(mine)) break;
@@ -1892,223 +1889,20 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
 #pragma unroll
     for (int k = 0; k < NPT; ++k) n0[k] = PgEv{0, 0, 0, 0, -1, 0, false};
     if (wv == 0) {
-      if (lane < K) {
-        int32_t m = -1, nn = 0, f = 0;
-#pragma unroll
-        for (int w = 0; w < PG2_NW; ++w) {
-          f += s_fit[w];
-          if (!s_cn[w][lane]) continue;
-          if (s_mx[w][lane] > m) { m = s_mx[w][lane]; nn = s_cn[w][lane]; }
-          else if (s_mx[w][lane] == m) nn += s_cn[w][lane];
-        }
-        const uint64_t v = ((uint64_t)tag << 56) | (lane == 0 ? ((uint64_t)f << 44) : 0) | ((uint64_t)nn << 32) |
-                           (uint64_t)(uint32_t)m;
-        pg_store(cls_at(g.gran, slot, lane, blockIdx.x), v);
-      }
+      pg_publish_classes<PG2_NW>(g, K, slot, tag, lane, s_fit, s_mx, s_cn);
 #ifdef KSIM_STAMPS
       t_pub = __builtin_amdgcn_s_memtime();
 #endif
-      // the decision's per-class map values (lane q = reduce class q)
-      int64_t tv_l = 0, av_l = 0, ad_l = 0;
-      if (lane < K) {
-        tv_l = X.tv(K > 1 ? lane / k2 : 0);
-        av_l = X.av(K > 1 ? lane % k2 : 0);
-        ad_l = X.ad(K > 1 ? lane % k2 : 0);
-      }
-      int mode = 0, blk = -1, rank = 0;
-      uint32_t win = 0;
-      int32_t tgt_l = -2;  // lane q: class q's maximum if q wins
-      // the workgroup holding the ix-th match from the top (lane-major workgroup order: lane l
-      // holds l, l + 64, ...; name rank grows with the workgroup index), bm = matches per workgroup
-      auto locate = [&](const int32_t (&bm)[MB], int64_t ix) {
-        // matches in workgroups above b = (lanes above, same m) + (every lane, higher m)
-        int64_t above = 0;
-        int found = -1, rk = 0;
-#pragma unroll
-        for (int m = MB - 1; m >= 0; --m) {
-        if (found < 0 && 64 * m < G) {
-          const int32_t pre = ksimw::prefix_incl_i32(bm[m]);
-          const int32_t tot = __builtin_amdgcn_readlane(pre, 63);
-          const int64_t ab = above + (int64_t)(tot - pre);
-          const bool hit = bm[m] > 0 && ix >= ab && ix < ab + bm[m];
-          const uint64_t hb = __ballot(hit);
-          if (hb) {
-            const int src = __builtin_ffsll((long long)hb) - 1;
-            found = src + 64 * m;
-            rk = (int)__builtin_amdgcn_readlane((int32_t)(ix - ab), src);
-          }
-          above += tot;
-        }
-        }
-        if (found < 0) { mode = -1; if (lane == 0) atomicOr(c.err, 2); }
-        blk = found;
-        rank = rk;
+      auto stamp = [&](int k) {
+#ifdef KSIM_STAMPS
+        if (k == 7) cs_acc += __builtin_amdgcn_s_memtime() - t_pub;
+#endif
+        if (blockIdx.x == 0 && tid == 0) PG_STAMP(k);
       };
-      if (K == 1) {
-        // one reduce class (no TaintToleration / NodeAffinity spread among the fit nodes): the
-        // class maximum is the best total, and only granule 0 of each workgroup is read
-        uint64_t gv0[MB];
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        bool ok = false;
-        for (;;) {
-          bool mine = true;
-#pragma unroll
-          for (int m = 0; m < MB; ++m) {
-            const int b = lane + 64 * m;
-            gv0[m] = b < G ? pg_load(cls_at(g.gran, slot, 0, b)) : ((uint64_t)tag << 56);
-            mine &= gtag(gv0[m]) == tag;
-          }
-          if (__all(mine)) { ok = true; break; }
-          if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-#ifdef KSIM_STAMPS
-        cs_acc += __builtin_amdgcn_s_memtime() - t_pub;
-        if (blockIdx.x == 0 && tid == 0) PG_STAMP(7);
-#endif
-        if (!ok) {
-          mode = -1;
-          if (lane == 0) atomicOr(c.err, 4);
-        } else {
-          int32_t f = 0, mm = -1, cc = 0;
-#pragma unroll
-          for (int m = 0; m < MB; ++m) {
-            if (lane + 64 * m >= G) continue;
-            f += gfit(gv0[m]);
-            const int32_t cn = gcnt(gv0[m]), sc0 = gscore(gv0[m]);
-            if (!cn) continue;
-            if (sc0 > mm) { mm = sc0; cc = cn; }
-            else if (sc0 == mm) cc += cn;
-          }
-          const int32_t F = ksimw::sum_i32(f);
-          if (F > 0) {
-            mode = 1;
-            int64_t ix = 0;
-            int32_t M0 = -1;
-            if (F > 1) {  // generic_scheduler.go:153-156: a single fit skips selectHost
-              mode = 2;
-              M0 = ksimw::max_i32(cc ? mm : -1);
-              const int32_t C = ksimw::sum_i32((cc && mm == M0) ? cc : 0);
-              win = 1;
-              tgt_l = lane == 0 ? M0 : -2;
-              ix = (counter >> 32) ? (int64_t)(counter % (uint64_t)C) : (int64_t)((uint32_t)counter % (uint32_t)C);
-              counter += 1;  // generic_scheduler.go:192-195
-            }
-            int32_t bm[MB];
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-              int32_t sb = 0;
-              if (lane + 64 * m < G)
-                sb = mode == 1 ? gfit(gv0[m]) : ((gcnt(gv0[m]) && gscore(gv0[m]) == M0) ? gcnt(gv0[m]) : 0);
-              bm[m] = sb;
-            }
-            locate(bm, ix);
-          }
-        }
-      } else {
-        uint64_t gv[KSIM_MAX_RCLASS][MB];
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        bool ok = false;
-        for (;;) {
-          bool mine = true;
-#pragma unroll
-          for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-              const int b = lane + 64 * m;
-              gv[q][m] = (q < K && b < G) ? pg_load(cls_at(g.gran, slot, q, b)) : ((uint64_t)tag << 56);
-              mine &= gtag(gv[q][m]) == tag;
-            }
-          }
-          if (__all(mine)) { ok = true; break; }
-          if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-#ifdef KSIM_STAMPS
-        cs_acc += __builtin_amdgcn_s_memtime() - t_pub;
-        if (blockIdx.x == 0 && tid == 0) PG_STAMP(7);
-#endif
-        if (!ok) {
-          mode = -1;
-          if (lane == 0) atomicOr(c.err, 4);
-        } else {
-          int32_t F = 0;
-          int32_t mq_l = -1, cq_l = 0;  // lane q: class q's global maximum and its count
-          int32_t f = 0;
-#pragma unroll
-          for (int m = 0; m < MB; ++m) f += (lane + 64 * m < G) ? gfit(gv[0][m]) : 0;
-          F = ksimw::sum_i32(f);
-#pragma unroll
-          for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-            if (q < K) {
-              int32_t mm = -1, cc = 0;
-#pragma unroll
-              for (int m = 0; m < MB; ++m) {
-                if (lane + 64 * m >= G) continue;
-                const int32_t cn = gcnt(gv[q][m]), s = gscore(gv[q][m]);
-                if (!cn) continue;
-                if (s > mm) { mm = s; cc = cn; }
-                else if (s == mm) cc += cn;
-              }
-              const int32_t Mq = ksimw::max_i32(cc ? mm : -1);
-              const int32_t Cq = ksimw::sum_i32((cc && mm == Mq) ? cc : 0);
-              mq_l = lane == q ? Mq : mq_l;
-              cq_l = lane == q ? Cq : cq_l;
-            }
-          }
-#ifdef KSIM_STAMPS
-          if (blockIdx.x == 0 && tid == 0) PG_STAMP(11);
-#endif
-          if (F > 0) {
-            mode = 1;
-            int64_t ix = 0;
-            if (F > 1) {  // generic_scheduler.go:153-156: a single fit skips selectHost
-              mode = 2;
-              // lane q = reduce class q: NormalizeReduce over the filtered set, weighted totals
-              // (reduce.go:29-64, generic_scheduler.go:632-639), the best total and its classes
-              const bool live = lane < K && cq_l != 0;
-              int64_t mxT = 0, mxA = 0;
-              // K <= 16: the class lanes are one DPP row
-              if (k1 > 1 || c.w[KSIM_W_TAINT_TOLERATION]) mxT = ksimw::max16_i64(live ? tv_l : 0);
-              if (k2 > 1 || c.w[KSIM_W_NODE_AFFINITY]) mxA = ksimw::max16_i64(live ? av_l : 0);
-              uint64_t t = (uint64_t)(int64_t)mq_l + (uint64_t)ad_l;
-              if (c.w[KSIM_W_TAINT_TOLERATION]) t += (uint64_t)c.w[KSIM_W_TAINT_TOLERATION] * (uint64_t)ksim_norm(tv_l, mxT, true);
-              if (c.w[KSIM_W_NODE_AFFINITY]) t += (uint64_t)c.w[KSIM_W_NODE_AFFINITY] * (uint64_t)ksim_norm(av_l, mxA, false);
-              const int64_t tot = live ? (int64_t)t : INT64_MIN;
-              const int64_t best = ksimw::max16_i64(tot);
-              const uint64_t wbm = __ballot(live && tot == best);
-              win = (uint32_t)wbm;
-              const int32_t C = ksimw::sum16_i32(((wbm >> lane) & 1ull) ? cq_l : 0);
-              tgt_l = ((wbm >> lane) & 1ull) ? mq_l : -2;
-              ix = (counter >> 32) ? (int64_t)(counter % (uint64_t)C) : (int64_t)((uint32_t)counter % (uint32_t)C);
-              counter += 1;  // generic_scheduler.go:192-195
-            }
-            // locate the workgroup holding the ix-th match from the top (lane-major workgroup order:
-            // lane l holds l, l + 64, ...; name rank grows with the workgroup index)
-            int32_t bm[MB];
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-              const int b = lane + 64 * m;
-              int32_t s = 0;
-              if (b < G) {
-                if (mode == 1) {
-                  s = gfit(gv[0][m]);
-                } else {
-#pragma unroll
-                  for (int q = 0; q < KSIM_MAX_RCLASS; ++q) {
-                    if (q < K && ((win >> q) & 1u)) {
-                      const int32_t Mq = __builtin_amdgcn_readlane(mq_l, q);
-                      if (gcnt(gv[q][m]) && gscore(gv[q][m]) == Mq) s += gcnt(gv[q][m]);
-                    }
-                  }
-                }
-              }
-              bm[m] = s;
-            }
-            locate(bm, ix);
-          }
-        }
-      }
+      int mode, blk, rank;
+      uint32_t win;
+      int32_t tgt_l;
+      pg_sweep_decide<MB>(c, g, X, K, k2, G, slot, tag, lane, counter, mode, blk, rank, win, tgt_l, stamp);
 #ifdef KSIM_STAMPS
       if (blockIdx.x == 0 && tid == 0) PG_STAMP(12);
 #endif
@@ -2212,7 +2006,7 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
       c.out_node[pod] = (int32_t)w;
       if (shared) {
         s_node = w;
-        pg_store(g.gran + PG_COMMIT_OFF + slot, ((uint64_t)tag << 56) | (uint64_t)w);
+        ksimx::store_agent(g.gran + PG_COMMIT_OFF + slot, ((uint64_t)tag << 56) | (uint64_t)w);
       }
     }
     PG_STAMP(4);
@@ -2233,7 +2027,7 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
       if (!owner && tid == 0) {
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         uint64_t v;
-        while (gtag(v = pg_load(g.gran + PG_COMMIT_OFF + slot)) != tag) {
+        while (gtag(v = ksimx::load_agent(g.gran + PG_COMMIT_OFF + slot)) != tag) {
           if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) { atomicOr(c.err, 4); s_abort = 1; break; }
           __builtin_amdgcn_s_sleep(1);
         }

@@ -17,6 +17,7 @@
 //   4. the owning thread commits (NodeInfo.AddPod, schedulercache/node_info.go:318-341) into the
 //      scenario's columns; the barrier's workgroup fence makes it visible to the next pod.
 // The node table streams from HBM every pod: the HBM-bandwidth-bound form of the scan.
+#include "ksim_decide.h"
 #include "ksim_sweep.h"
 #include "ksim_wave.h"
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(SB) void ksim_sweep_kernel(SwArgs a) {
       __syncthreads();  // s_red is rewritten by the next pod
       continue;
     }
-    const uint32_t ix = (F > 1) ? (uint32_t)((counter >> 32) ? counter % (uint64_t)C : (uint32_t)counter % (uint32_t)C) : 0u;
+    const uint32_t ix = (F > 1) ? (uint32_t)ksim_select_ix(counter, (uint32_t)C) : 0u;
     counter += (F > 1) ? 1 : 0;  // generic_scheduler.go:192-195 (selectHost only when F > 1)
     // ---- 3. the ix-th row at M from the top ----
     int32_t c_t = 0;

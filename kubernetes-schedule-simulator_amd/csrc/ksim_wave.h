@@ -1,7 +1,7 @@
 // ksim_wave.h — wave64 reductions and scans on DPP (gfx9-family row controls: quad_perm,
 // row_shr, row_(half_)mirror, row_bcast15/31) instead of ds_bpermute shuffles: each step is
 // one VALU op with a DPP source instead of an LDS-crossbar round trip.  Results are
-// checked against naive lane loops by ksim_selftest_wave() (tests/test_gpu_parity.py).
+// checked against naive lane loops by ksim_selftest() (tests/test_gpu_parity.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

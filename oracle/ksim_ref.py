@@ -1922,12 +1922,13 @@ def expand_simulation_pods(spec_list):
 
 
 def simulate(nodes, running_pods, sim_pods, predicate_keys, priority_configs, custom_predicates=None, spread=None,
-             custom_priorities=None):
+             custom_priorities=None, last_node_index=0):
     """Runs the ClusterCapacity loop: pods are popped LIFO (store.go:223-233),
     each is scheduled, bound pods are assumed into the node cache (scheduler.go:366
     → cache.go:125 → node_info.go:318), unschedulable pods are recorded and the
     loop continues (simulator.go:163-185) until the queue is empty.
-    Returns list of (pod_name, node_name or None, fit_error_message or None)."""
+    last_node_index: genericScheduler.lastNodeIndex at the start.
+    Returns list of (pod_name, node_name or None, fit_error_message or None) and the final lastNodeIndex."""
     infos = [NodeInfo(n) for n in nodes]
     by_name = {ni.name: ni for ni in infos}
     for p in running_pods:
@@ -1936,6 +1937,7 @@ def simulate(nodes, running_pods, sim_pods, predicate_keys, priority_configs, cu
             by_name[nn].add_pod(p)
     sched = GenericScheduler(predicate_keys, priority_configs, custom_predicates, spread=spread,
                              custom_priorities=custom_priorities)
+    sched.last_node_index = last_node_index
     queue = list(sim_pods)
     out = []
     while queue:

@@ -117,6 +117,55 @@ def test_simulation_matches_oracle(seed, policy, mode):
     assert rep.last_node_index == want_lni
 
 
+CROSS_START = 2**32 - 4  # lastNodeIndex before the first pod: selectHost's 64-bit index after four more
+
+
+def _crossing_workload():
+    """12 pods under the "weighted" policy (more than one reduce class) from a counter that passes
+    2^32 during the run: the oracle's placements and final lastNodeIndex, and the ingested cluster.
+    (Seed 5: the oracle with its counter cut to 32 bits places these pods differently.)"""
+    nodes, running, pods = rnd_workload(5, n_nodes=23, n_pods=12)
+    preds, prios = POLICIES["weighted"]
+    want, want_lni = R.simulate(nodes, running, pods, set(preds), list(prios), last_node_index=CROSS_START)
+    # the counter moves once per pod with more than one fit node: at least 6 of them, so it crosses
+    assert want_lni - CROSS_START >= 6 and want_lni > 2**32
+    cl = ingest.Cluster.from_objects(nodes, running, list(reversed(pods)))
+    return cl, preds, prios, want, want_lni
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_counter_crossing_2_32_matches_oracle(mode):
+    cl, preds, prios, want, want_lni = _crossing_workload()
+    g = scheduler.GenericScheduler(cl, preds, prios, mode=mode, last_node_index=CROSS_START)
+    try:
+        assert int((np.asarray(g.tables["n_tt"]) * np.asarray(g.tables["n_na"]))[np.asarray(cl.pods["cls"])].max()) > 1
+        out, reasons, _ = g.schedule()
+        got = [(cl.pod_names[k], cl.names[w] if w >= 0 else None,
+                None if w >= 0 else scheduler.fit_error_message(cl.n_nodes, reasons[k], cl.scalar_names.items))
+               for k, w in enumerate(out)]
+        assert got == want
+        assert g.last_node_index == want_lni
+    finally:
+        g.close()
+
+
+def test_counter_crossing_2_32_schedule_one():
+    """The same pods one ksim_schedule_one call each: the per-pod kernels' 64-bit index."""
+    import ctypes as C
+    cl, preds, prios, want, want_lni = _crossing_workload()
+    one = scheduler.GenericScheduler(cl, preds, prios, mode=abi.MODE_LAUNCH, last_node_index=CROSS_START)
+    try:
+        for k, (_, host, _) in enumerate(want):
+            pod = abi.Pod.from_buffer_copy(cl.pods[k].tobytes())
+            res = abi.Result()
+            one.h.call("ksim_schedule_one", C.byref(pod), abi.vptr(cl.pod_ports), len(cl.pod_ports),
+                       abi.vptr(cl.pod_scalars), len(cl.pod_scalars), abi.SCHEDULE_ASSUME, C.byref(res))
+            assert (cl.names[res.node] if res.node >= 0 else None) == host, k
+        assert one.last_node_index == want_lni
+    finally:
+        one.close()
+
+
 PA_POLICIES = {
     "default": scheduler.provider("DefaultProvider"),
     "pa_only": (["GeneralPredicates"], [("NodePreferAvoidPodsPriority", 3)]),
