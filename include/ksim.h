@@ -320,6 +320,24 @@ int ksim_evaluate(ksim_handle* h, int64_t pod, uint8_t* out_fit, uint32_t* out_r
 int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count,
                int32_t* out_node, uint64_t* out_counters, ksim_stats* stats);
 
+/* ksim_sweep with a node set per scenario — the node-outage what-if (N-1 failure, zone or rack
+ * drain, scale-up candidates loaded and left out where not bought).  Scenario s is the run on the
+ * snapshot from which its absent nodes were left out: they are not listed (never evaluated, not
+ * counted in len(filtered), never scored or selected, whatever predicates are configured — not the
+ * same as flagging them unschedulable), pods already on them are gone with them, the name order of
+ * the remaining nodes is unchanged (selectHost counts over the listed nodes only), lastNodeIndex
+ * advances as always, and placements are name ranks of the loaded table.  A scenario without any
+ * node yields -1 for every pod and the starting counter.
+ * absent: [n_scen][ceil(n_nodes/32)] words, bit (j & 31) of word (j >> 5) set = node j (name rank)
+ * is not listed in that scenario; bits at or above n_nodes are ignored; NULL = no node absent (then
+ * identical to ksim_sweep).  weights: as ksim_sweep, or NULL = every scenario runs under the
+ * handle's own configured weights (its reduce and constant priorities are one value on every node
+ * for resource-only pods and drop out of the choice).  out_scheduled (optional): [n_scen] pods
+ * bound.  Every refusal of ksim_sweep applies; the handle's own state is left unchanged. */
+int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
+                     int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters,
+                     int32_t* out_scheduled, ksim_stats* stats);
+
 /* ---- Node-sharded scheduling of one cluster across devices ----
  * Rank r of `world` (one handle per device, one process or thread each) loads the contiguous
  * name-rank shard [node_base, node_base + n_r) of the node table and the whole pod queue.

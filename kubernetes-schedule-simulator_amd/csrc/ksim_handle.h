@@ -42,7 +42,8 @@ extern "C" hipError_t ksim_sweep_prepare(const int64_t* ac, const int64_t* am, i
                                          double* yc, double* ym, hipStream_t st);
 extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, const int64_t* zc0, const int64_t* zm0,
                                         const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgs* args,
-                                        int32_t n_scen, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
+                                        int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
+                                        hipEvent_t ev1, hipStream_t st);
 extern "C" int ksim_pfast_config(int64_t n, int max_grid, int stream, int* grid, int* lds_rows);
 extern "C" hipError_t ksim_pstream_prepare(const KsimCtx* c, double* mirror, hipStream_t s);
 extern "C" size_t ksim_pfast_granule_bytes(void);
@@ -55,7 +56,12 @@ extern "C" hipError_t ksim_launch_pfast(const KsimCtx* c, uint64_t* granules, in
 extern "C" hipError_t ksim_tree_build(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
                                       const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
                                       double* ty, const KsimTreeSweep* sw, hipStream_t s);
+extern "C" hipError_t ksim_tree_build_absent(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
+                                             const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
+                                             double* ty, const KsimTreeSweep* sw, hipStream_t s);
 extern "C" hipError_t ksim_tree_sweep_init(const KsimCtx* c, const KsimTreeSweep* sw, hipStream_t s);
+extern "C" hipError_t ksim_tree_sweep_absent(const KsimCtx* c, const KsimTreeSweep* sw, const uint32_t* absent,
+                                             int32_t words, hipStream_t s);
 extern "C" hipError_t ksim_tree_launch(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
                                        const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
                                        double* ty, const KsimTreeSweep* sw, hipStream_t s);

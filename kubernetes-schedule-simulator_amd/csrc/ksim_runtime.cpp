@@ -1472,34 +1472,50 @@ int ksim_evaluate(ksim_handle* h, int64_t pod, uint8_t* out_fit, uint32_t* out_r
   return KSIM_OK;
 }
 
-int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count, int32_t* out_node,
-               uint64_t* out_counters, ksim_stats* st) {
-  if (!h || !weights || !out_node) return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep: null argument");
-  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "ksim_sweep: load nodes, classes and pods first");
+// per-scenario pods bound (ksim_sweep_nodes out_scheduled)
+static void sweep_scheduled(const int32_t* out_node, int32_t n_scen, int64_t count, int32_t* out_scheduled) {
+  if (!out_scheduled) return;
+  for (int32_t s = 0; s < n_scen; ++s) {
+    int32_t b = 0;
+    for (int64_t k = 0; k < count; ++k) b += out_node[(size_t)s * count + k] >= 0;
+    out_scheduled[s] = b;
+  }
+}
+
+// ksim_sweep (absent = NULL, weights given) and ksim_sweep_nodes.  absent: [n_scen][ceil(n / 32)]
+// words, a set bit = the node is not listed in that scenario; weights NULL = the handle's own.
+static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
+                      int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
+                      ksim_stats* st) {
+  if (!h || !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
+  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
   if (n_scen <= 0 || first < 0 || count <= 0 || first + count > h->n_pods || count > INT32_MAX)
-    return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep: bad scenario count or pod range");
+    return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
   HIPCHK(h, hipSetDevice(h->device));
   KsimCtx& c = h->ctx;
   const int64_t n = c.n;
   if (n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (int rc0 = ksim_rt_check_aff(h, "ksim_sweep")) return rc0;
+  if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
   if (n > KSIM_SWEEP_MAX_NODES)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "ksim_sweep: %lld nodes exceed the %d-node scenario layout", (long long)n,
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout", who, (long long)n,
                 KSIM_SWEEP_MAX_NODES);
   if (h->fast_pre[first + count] - h->fast_pre[first] != count)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "ksim_sweep: every pod must be resource-only (no ports, selectors, taints, "
-                                       "nodeName, gpu / ephemeral / extended requests)");
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: every pod must be resource-only (no ports, selectors, taints, "
+                                       "nodeName, gpu / ephemeral / extended requests)", who);
   std::vector<int32_t> w3((size_t)n_scen * 3);
   for (int32_t sidx = 0; sidx < n_scen; ++sidx) {
-    const int64_t* w = weights + (size_t)sidx * KSIM_NW;
-    if (w[KSIM_W_TAINT_TOLERATION] || w[KSIM_W_NODE_AFFINITY])
-      return ksim_fail(h, KSIM_E_UNSUPPORTED, "ksim_sweep: scenario %d: reduce priorities are not swept", sidx);
+    // weights NULL: the handle's own map weights.  Its reduce and constant priorities are the same
+    // value on every node for the pods admitted above (fast_k: one reduce class) and stay out of
+    // the packed score, as in the fast persistent kernel.
+    const int64_t* w = weights ? weights + (size_t)sidx * KSIM_NW : c.w;
+    if (weights && (w[KSIM_W_TAINT_TOLERATION] || w[KSIM_W_NODE_AFFINITY]))
+      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: reduce priorities are not swept", who, sidx);
     int64_t tot = 0;
     for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED}) {
-      if (w[k] < 0 || w[k] > 6553) return ksim_fail(h, KSIM_E_UNSUPPORTED, "ksim_sweep: scenario %d: weight out of range", sidx);
+      if (w[k] < 0 || w[k] > 6553) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
       tot += w[k];
     }
-    if (tot * 10 >= 0xFFFF) return ksim_fail(h, KSIM_E_UNSUPPORTED, "ksim_sweep: scenario %d: scores exceed 16 bits", sidx);
+    if (tot * 10 >= 0xFFFF) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: scores exceed 16 bits", who, sidx);
     w3[3 * sidx] = (int32_t)w[KSIM_W_LEAST_REQUESTED];
     w3[3 * sidx + 1] = (int32_t)w[KSIM_W_MOST_REQUESTED];
     w3[3 * sidx + 2] = (int32_t)w[KSIM_W_BALANCED];
@@ -1516,9 +1532,10 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
     }
     const int64_t lim = (int64_t)1 << 48;
     if (nmax >= lim || qmax >= lim || count > lim / std::max<int64_t>(qmax, 1) || nmax + count * qmax >= lim)
-      return ksim_fail(h, KSIM_E_UNSUPPORTED, "ksim_sweep: quantities may leave the exact float64 range (2^48)");
+      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: quantities may leave the exact float64 range (2^48)", who);
   }
   int rc;
+  const int32_t aw = (int32_t)((n + 31) / 32);  // node-set words per scenario
   // Tree form (ksim_tree.hip): one tree-mode wave per scenario, scenarios spread over the CUs.
   if (!getenv("KSIM_SWEEP_SCAN") && h->n_tcls > 0 && n < ((int64_t)1 << 24) && !h->pfast_off) {
     KsimTreeGeo g{};
@@ -1528,8 +1545,9 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
       if (!h->t_y && (rc = dev_alloc(h, &h->t_y, (size_t)2 * n))) return rc;
       auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
       const size_t N = (size_t)n, P = (size_t)count, K = (size_t)g.K;
+      const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
       const size_t per = al(4 * N * 8) + al(N * 4) + al(K * g.st[0] * 4) + al(g.level_entries * 8) + al(K * 4) + al(8) +
-                         al(P * 4) + al(sizeof(kf64::EvCfg));
+                         al(P * 4) + al(sizeof(kf64::EvCfg)) + (MW ? al(MW) : 0);
       // scratch budget: at most 24 GiB (all 4,096 C5 scenarios, ~3.7 MB each, in one launch) and
       // at most half of the device memory free now (a shared or smaller device gets smaller chunks)
       size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
@@ -1538,7 +1556,7 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
       if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
       auto need_of = [&](size_t C) {
         return C * (al(4 * N * 8) + al(N * 4)) + al(C * K * g.st[0] * 4) + al(C * g.level_entries * 8) + al(C * K * 4) +
-               al(C * 8) + al(C * P * 4) + al(C * sizeof(kf64::EvCfg)) + 4096;
+               al(C * 8) + al(C * P * 4) + al(C * sizeof(kf64::EvCfg)) + (MW ? al(C * MW) : 0) + 4096;
       };
       if (h->swt_bytes < need_of((size_t)chunk)) {
         if (h->swt_scratch) {
@@ -1559,7 +1577,7 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
             break;
           }
           (void)hipGetLastError();
-          if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "ksim_sweep: no device memory for one scenario (%zu bytes)", need);
+          if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "%s: no device memory for one scenario (%zu bytes)", who, need);
           chunk = (chunk + 1) / 2;
         }
       }
@@ -1578,6 +1596,7 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
       sw.out_node = (int32_t*)take(C * P * 4);
       kf64::EvCfg* dcfg = (kf64::EvCfg*)take(C * sizeof(kf64::EvCfg));
       sw.cfg = dcfg;
+      uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
       std::vector<kf64::EvCfg> cfgs((size_t)n_scen);
       for (int32_t sidx = 0; sidx < n_scen; ++sidx)
         cfgs[sidx] = kf64::make_evcfg(c.preds, c.no_prio != 0, w3[3 * sidx], w3[3 * sidx + 1], w3[3 * sidx + 2]);
@@ -1591,8 +1610,13 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
         sw.nsc = std::min(chunk, n_scen - s0);
         HIPCHK(h, hipMemcpyAsync(dcfg, cfgs.data() + s0, sw.nsc * sizeof(kf64::EvCfg), hipMemcpyHostToDevice, ksim_stream(h)));
         HIPCHK(h, hipEventRecord(h->ev0, ksim_stream(h)));
+        if (absent)
+          HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)sw.nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
         hipError_t e = ksim_tree_sweep_init(&c, &sw, ksim_stream(h));
-        if (e == hipSuccess) e = ksim_tree_build(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h));
+        if (e == hipSuccess && absent) e = ksim_tree_sweep_absent(&c, &sw, dabs, aw, ksim_stream(h));
+        if (e == hipSuccess)
+          e = absent ? ksim_tree_build_absent(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h))
+                     : ksim_tree_build(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h));
         if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "tree sweep build: %s", hipGetErrorString(e));
         HIPCHK(h, hipEventRecord(h->ev1, ksim_stream(h)));
         e = ksim_tree_launch(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h));
@@ -1631,6 +1655,7 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
         st->mode = KSIM_MODE_TREE;
         st->blocks = chunk;
       }
+      sweep_scheduled(out_node, n_scen, count, out_scheduled);
       return KSIM_OK;
     }
   }
@@ -1641,13 +1666,22 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
     hipError_t e = ksim_sweep_prepare(c.alloc_cpu, c.alloc_mem, n, h->sw_dac, h->sw_dam, h->sw_yc, h->sw_ym, ksim_stream(h));
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep prepare: %s", hipGetErrorString(e));
   }
-  // scratch: [S][n] x (4 float64 + int32), pods, weights, outputs
+  // scratch: [C][n] x (4 float64 + int32) and outputs for a chunk of C scenarios, the pods and every
+  // scenario's weights.  The chunk follows the tree form's rule: at most 24 GiB and at most half
+  // of the device memory free now, halved while the allocation fails; one chunk is one launch.
   const size_t S = (size_t)n_scen, N = (size_t)n, P = (size_t)count;
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_dyn = al(S * N * 8), b_cnt = al(S * N * 4), b_pod = al(P * sizeof(kf64::FPod)), b_w = al(S * 12),
-               b_out = al(S * P * 4), b_ctr = al(S * 8);
-  const size_t need = 4 * b_dyn + b_cnt + b_pod + b_w + b_out + b_ctr;
-  if (h->sw_scratch_bytes < need) {
+  const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
+  const size_t b_pod = al(P * sizeof(kf64::FPod)), b_w = al(S * 12);
+  auto need_of = [&](size_t C) {
+    return 4 * al(C * N * 8) + al(C * N * 4) + b_pod + b_w + al(C * P * 4) + al(C * 8) + (MW ? al(C * MW) : 0);
+  };
+  size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
+  if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
+  const size_t per = N * 36 + P * 4 + 8 + MW;
+  int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
+  if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
+  if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
     if (h->sw_scratch) {
       for (auto& b : h->bufs)
         if (b.p == h->sw_scratch) b.p = nullptr;
@@ -1656,35 +1690,54 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
       h->sw_scratch_bytes = 0;
     }
     char* p = nullptr;
-    if ((rc = dev_alloc(h, &p, need))) return rc;
-    h->sw_scratch = p;
-    h->sw_scratch_bytes = need;
+    for (;;) {
+      const size_t need = need_of((size_t)chunk);
+      if (hipMalloc((void**)&p, need) == hipSuccess) {
+        h->bufs.push_back({p, need});
+        h->sw_scratch = p;
+        h->sw_scratch_bytes = need;
+        break;
+      }
+      (void)hipGetLastError();
+      if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "%s: no device memory for one scenario (%zu bytes)", who, need);
+      chunk = (chunk + 1) / 2;
+    }
   }
-  char* base = (char*)h->sw_scratch;
+  const size_t C = (size_t)chunk;
+  char* q = (char*)h->sw_scratch;
+  auto take = [&](size_t b) { char* r = q; q += al(b); return r; };
   SwArgs a{};
-  a.n = n; a.n_pods = (int32_t)count; a.scen0 = 0;
+  a.n = n; a.n_pods = (int32_t)count;
   a.dac = h->sw_dac; a.dam = h->sw_dam; a.yc = h->sw_yc; a.ym = h->sw_ym;
   a.allowed = c.allowed_pods; a.flags = c.flags;
-  a.rc = (double*)base; a.rm = (double*)(base + b_dyn); a.zc = (double*)(base + 2 * b_dyn);
-  a.zm = (double*)(base + 3 * b_dyn);
-  a.count = (int32_t*)(base + 4 * b_dyn);
-  char* q = base + 4 * b_dyn + b_cnt;
-  a.pods = (const kf64::FPod*)q;
-  int32_t* dw = (int32_t*)(q + b_pod);
+  a.rc = (double*)take(C * N * 8); a.rm = (double*)take(C * N * 8);
+  a.zc = (double*)take(C * N * 8); a.zm = (double*)take(C * N * 8);
+  a.count = (int32_t*)take(C * N * 4);
+  a.pods = (const kf64::FPod*)take(P * sizeof(kf64::FPod));
+  int32_t* dw = (int32_t*)take(S * 12);
   a.w = dw;
-  a.out_node = (int32_t*)(q + b_pod + b_w);
-  a.out_counter = (uint64_t*)(q + b_pod + b_w + b_out);
+  a.out_node = (int32_t*)take(C * P * 4);
+  a.out_counter = (uint64_t*)take(C * 8);
+  uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
   a.preds = c.preds; a.no_prio = c.no_prio;
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 12, hipMemcpyHostToDevice, ksim_stream(h)));
-  hipError_t e = ksim_sweep_launch(c.req_cpu, c.req_mem, c.nz_cpu, c.nz_mem, c.pod_count, c.pods + first,
-                                   (void*)a.pods, &a, n_scen, h->ev0, h->ev1, ksim_stream(h));
-  if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
-  HIPCHK(h, hipEventSynchronize(h->ev1));
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  HIPCHK(h, hipMemcpy(out_node, a.out_node, S * P * 4, hipMemcpyDeviceToHost));
-  if (out_counters) HIPCHK(h, hipMemcpy(out_counters, a.out_counter, S * 8, hipMemcpyDeviceToHost));
+  for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
+    const int32_t nsc = std::min(chunk, n_scen - s0);
+    a.scen0 = s0;  // the chunk's first scenario: its row of the weights
+    if (absent)
+      HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
+    hipError_t e = ksim_sweep_launch(c.req_cpu, c.req_mem, c.nz_cpu, c.nz_mem, c.pod_count, c.pods + first,
+                                     (void*)a.pods, &a, nsc, dabs, aw, h->ev0, h->ev1, ksim_stream(h));
+    if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
+    HIPCHK(h, hipEventSynchronize(h->ev1));
+    float c_ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
+    ms += c_ms;
+    HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
+    if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
+  }
   if (st) {
     memset(st, 0, sizeof *st);
     st->pods = (int64_t)(S * P);
@@ -1694,11 +1747,24 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
     st->node_evals = (int64_t)(S * P) * n;
     st->device_ms = ms;
     st->kernel_ms = ms;
-    st->kernel_launches = 1;
+    st->kernel_launches = (n_scen + chunk - 1) / chunk;
     st->mode = KSIM_MODE_PERSISTENT;
-    st->blocks = n_scen;
+    st->blocks = chunk;
   }
+  sweep_scheduled(out_node, n_scen, count, out_scheduled);
   return KSIM_OK;
+}
+
+int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count, int32_t* out_node,
+               uint64_t* out_counters, ksim_stats* st) {
+  if (!weights) return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep: null argument");
+  return sweep_impl(h, "ksim_sweep", weights, nullptr, n_scen, first, count, out_node, out_counters, nullptr, st);
+}
+
+int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
+                     int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled, ksim_stats* st) {
+  return sweep_impl(h, "ksim_sweep_nodes", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
+                    st);
 }
 
 int ksim_shard_setup(ksim_handle* h, int32_t rank, int32_t world, int64_t node_base) {

@@ -17,6 +17,13 @@
 //   4. the owning thread commits (NodeInfo.AddPod, schedulercache/node_info.go:318-341) into the
 //      scenario's columns; the barrier's workgroup fence makes it visible to the next pod.
 // The node table streams from HBM every pod: the HBM-bandwidth-bound form of the scan.
+//
+// Node sets per scenario (ksim_sweep_nodes): once the scenario's columns are initialised, the sign
+// bit of its pod-count entry is set for every node the scenario does not list, and the ABS
+// instantiation of the scan maps a negative count to "does not fit".  Such a row is NOFIT in
+// LDS, so F, M, C and the select prefix run over the listed nodes only, and a commit, which
+// lands on a fit row, never touches the bit.  Without a node set the ABS = false instantiation
+// runs.
 #include "ksim_decide.h"
 #include "ksim_sweep.h"
 #include "ksim_wave.h"
@@ -30,6 +37,7 @@ constexpr uint16_t NOFIT = 0xFFFF;
 }  // namespace
 
 
+template <bool ABS>
 __global__ __launch_bounds__(SB) void ksim_sweep_kernel(SwArgs a) {
   extern __shared__ uint16_t sc[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
@@ -60,7 +68,8 @@ __global__ __launch_bounds__(SB) void ksim_sweep_kernel(SwArgs a) {
       r.rc = rc[j]; r.rm = rm[j]; r.zc = zc[j]; r.zm = zm[j];
       r.allowed = a.allowed[j]; r.count = cnt[j]; r.fl = a.flags[j];
       uint32_t rmask;
-      const int32_t e = feval(EC, P, r, rmask);
+      int32_t e = feval(EC, P, r, rmask);
+      if constexpr (ABS) e = r.count < 0 ? -1 : e;  // a node this scenario does not list
       sc[j] = e < 0 ? NOFIT : (uint16_t)e;
       f += e >= 0 ? 1 : 0;
       cm = e > mx ? 1 : cm + ((e == mx && e >= 0) ? 1 : 0);
@@ -136,6 +145,15 @@ __global__ void ksim_sweep_init_kernel(const int64_t* rc0, const int64_t* rm0, c
   rc[k] = (double)rc0[i]; rm[k] = (double)rm0[i]; zc[k] = (double)zc0[i]; zm[k] = (double)zm0[i]; c[k] = c0[i];
 }
 
+// node sets: absent holds [scenarios][words] bits, bit (i & 31) of word (i >> 5) set = node i is
+// not listed in that scenario -> the sign bit of its pod count in the scenario's column
+__global__ void ksim_sweep_absent_kernel(const uint32_t* absent, int32_t words, int64_t n, int64_t total, int32_t* c) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= total) return;
+  const int64_t i = k % n;
+  if ((absent[(k / n) * words + (i >> 5)] >> (i & 31)) & 1u) c[k] |= INT32_MIN;
+}
+
 __global__ void ksim_sweep_pods_kernel(const ksim_pod* pods, int64_t count, FPod* out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) out[i] = load_fpod(pods[i]);
@@ -152,16 +170,23 @@ extern "C" hipError_t ksim_sweep_prepare(const int64_t* ac, const int64_t* am, i
 
 extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, const int64_t* zc0, const int64_t* zm0,
                                         const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgs* args,
-                                        int32_t n_scen, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
+                                        int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
+                                        hipEvent_t ev1, hipStream_t st) {
   const int64_t n = args->n, total = n * (int64_t)n_scen;
   hipLaunchKernelGGL(ksim_sweep_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, rc0, rm0, zc0, zm0,
                      c0, n, total, args->rc, args->rm, args->zc, args->zm, args->count);
+  if (absent)
+    hipLaunchKernelGGL(ksim_sweep_absent_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, absent,
+                       absent_words, n, total, args->count);
   hipLaunchKernelGGL(ksim_sweep_pods_kernel, dim3((unsigned)((args->n_pods + 255) / 256)), dim3(256), 0, st, pods,
                      (int64_t)args->n_pods, (FPod*)fpods);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ev0) (void)hipEventRecord(ev0, st);
-  hipLaunchKernelGGL(ksim_sweep_kernel, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
+  if (absent)
+    hipLaunchKernelGGL(ksim_sweep_kernel<true>, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
+  else
+    hipLaunchKernelGGL(ksim_sweep_kernel<false>, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;

@@ -198,6 +198,11 @@ __device__ __forceinline__ uint32_t mod_u64(uint64_t x, uint32_t c) {
 }
 
 // ---------------------------------------------------------------- tree build (per call if stale)
+// ABS (ksim_sweep_nodes): a node the scenario does not list carries the sign bit in the
+// scenario's pod-count column (ksim_tree_sweep_absent) and is a -1 leaf in every class's tree.
+// The fit counts then count listed nodes only, and the per-pod kernel, which re-evaluates only
+// the node it committed to (a fit one), never meets such a row.
+template <bool ABS>
 __global__ __launch_bounds__(256) void ksim_tree_leaf_kernel(TreeArgs a0) {
   const int64_t st0 = a0.g.st[0], per = (int64_t)a0.g.K * st0, tot = per * max(1, a0.nsc);
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x) {
@@ -210,7 +215,13 @@ __global__ __launch_bounds__(256) void ksim_tree_leaf_kernel(TreeArgs a0) {
     int32_t v = -1;
     if (i < a.g.n) {
       uint32_t rmask;
-      v = kf64::feval(a.cfg, class_pod(a.cls[k]), load_row(a, i), rmask);
+      if constexpr (ABS) {
+        const kf64::FRow row = load_row(a, i);
+        v = kf64::feval(a.cfg, class_pod(a.cls[k]), row, rmask);
+        v = row.count < 0 ? -1 : v;
+      } else {
+        v = kf64::feval(a.cfg, class_pod(a.cls[k]), load_row(a, i), rmask);
+      }
     }
     a.leaves[r] = v;
     if (sc == 0 && k == 0 && i < a.g.n) {
@@ -663,6 +674,24 @@ __global__ __launch_bounds__(256) void ksim_tree_sweep_init_kernel(const int64_t
   }
 }
 
+// node sets: bit (i & 31) of word (i >> 5) of absent[scenario] set = node i is not listed in
+// that scenario -> the sign bit of its pod count in the scenario's column
+__global__ __launch_bounds__(256) void ksim_tree_sweep_absent_kernel(const uint32_t* absent, int32_t words, int64_t n,
+                                                                      int64_t tot, int32_t* count) {
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t % n;
+    if ((absent[(t / n) * words + (i >> 5)] >> (i & 31)) & 1u) count[t] |= INT32_MIN;
+  }
+}
+
+extern "C" hipError_t ksim_tree_sweep_absent(const KsimCtx* c, const KsimTreeSweep* sw, const uint32_t* absent,
+                                             int32_t words, hipStream_t s) {
+  const int64_t tot = c->n * sw->nsc;
+  hipLaunchKernelGGL(ksim_tree_sweep_absent_kernel, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 16384)), dim3(256), 0,
+                     s, absent, words, c->n, tot, sw->count);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t ksim_tree_sweep_init(const KsimCtx* c, const KsimTreeSweep* sw, hipStream_t s) {
   const int64_t tot = c->n * sw->nsc;
   hipLaunchKernelGGL(ksim_tree_sweep_init_kernel, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 16384)), dim3(256), 0, s,
@@ -714,20 +743,34 @@ extern "C" int ksim_tree_plan(int64_t n, int32_t K, int64_t budget, int32_t forc
   return found ? 1 : 0;
 }
 
-extern "C" hipError_t ksim_tree_build(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
-                                      const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
-                                      double* ty, const KsimTreeSweep* sw, hipStream_t s) {
+template <bool ABS>
+static hipError_t tree_build(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls, const int32_t* tcls,
+                             int32_t* leaves, uint64_t* levels, int32_t* fitc, double* ty, const KsimTreeSweep* sw,
+                             hipStream_t s) {
   const TreeArgs a = make_args(c, g, cls, tcls, leaves, levels, fitc, ty, sw);
   const int nsc = a.nsc;
   const int64_t ns = std::max(1, nsc);
   const int64_t tl = (int64_t)g->K * g->st[0] * ns;
-  hipLaunchKernelGGL(ksim_tree_leaf_kernel, dim3((unsigned)std::min<int64_t>((tl + 255) / 256, 8192)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(ksim_tree_leaf_kernel<ABS>, dim3((unsigned)std::min<int64_t>((tl + 255) / 256, 8192)), dim3(256), 0, s, a);
   for (int h = 1; h <= g->H; ++h) {
     const int64_t waves = (int64_t)g->K * g->st[h] * ns;
     hipLaunchKernelGGL(ksim_tree_level_kernel, dim3((unsigned)std::min<int64_t>((waves + 3) / 4, 8192)), dim3(256), 0, s, a, h);
   }
   hipLaunchKernelGGL(ksim_tree_fit_kernel, dim3((unsigned)(g->K * ns)), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+extern "C" hipError_t ksim_tree_build(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
+                                      const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
+                                      double* ty, const KsimTreeSweep* sw, hipStream_t s) {
+  return tree_build<false>(c, g, cls, tcls, leaves, levels, fitc, ty, sw, s);
+}
+
+// the build of a sweep whose scenarios carry node sets (ksim_tree_sweep_absent ran on sw->count)
+extern "C" hipError_t ksim_tree_build_absent(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
+                                             const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
+                                             double* ty, const KsimTreeSweep* sw, hipStream_t s) {
+  return tree_build<true>(c, g, cls, tcls, leaves, levels, fitc, ty, sw, s);
 }
 
 extern "C" hipError_t ksim_tree_launch(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,

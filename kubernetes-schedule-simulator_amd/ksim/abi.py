@@ -189,7 +189,7 @@ EXPORTS = ["ksim_abi_version", "ksim_last_error", "ksim_create", "ksim_destroy",
            "ksim_shard_setup", "ksim_shard_export", "ksim_shard_connect", "ksim_shard_connect_local",
            "ksim_schedule_one", "ksim_pod_add", "ksim_pod_remove", "ksim_node_add", "ksim_node_update",
            "ksim_node_remove", "ksim_node_count", "ksim_append_pods", "ksim_load_affinity", "ksim_load_volumes",
-           "ksim_read_volumes", "ksim_grow_volumes"]
+           "ksim_read_volumes", "ksim_grow_volumes", "ksim_sweep_nodes"]
 IPC_HANDLE_BYTES = 64
 MAX_RANKS = 8
 
@@ -241,6 +241,8 @@ def lib():
     L.ksim_shard_connect_local.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.ksim_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                              C.POINTER(Stats)]
+    L.ksim_sweep_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     podargs = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     L.ksim_schedule_one.argtypes = [C.c_void_p] + podargs + [C.c_int32, C.POINTER(Result)]
     L.ksim_pod_add.argtypes = [C.c_void_p, C.c_int64] + podargs

@@ -3,6 +3,7 @@
     python -m ksim.cli --podspec etc/pod.yaml --nodes nodes.json [--pods pods.json]
                        [--algorithmprovider DefaultProvider | --policy-config-file policy.json]
                        [--namespace NS] [--uuid-names] [--json]
+                       [--what-if-outage node|LABEL-KEY [--what-if-json]]
 
 Reference: cmd/app/server.go:40-110 (flags from cmd/app/options/options.go:64-69, podspec parsing
 :73-99, run + ClusterCapacityReviewPrint) and the offline checkpoint path of pkg/main.go:134-179
@@ -11,6 +12,12 @@ files: listing a live cluster through --kubeconfig needs an API server and is ou
 (SURVEY.md §8), so that flag is refused rather than ignored.  Pods in pods.json are the
 already-running pods (getCheckpoints lists status.phase=Running; here the file is taken as it
 is, like anaCheckPoint).  Exit status 1 with a message on every error, like glog.Fatalf.
+
+--what-if-outage KEY adds, after the normal report, the node-outage what-ifs of the snapshot
+(ClusterCapacity.what_if): KEY = node removes each node in turn (N-1), any other KEY removes the
+nodes of each value of that node label in turn (a zone or rack drain).  One line per outage with
+its name, the nodes removed and the pods scheduled and failed; --what-if-json prints the records
+as JSON instead.
 """
 from __future__ import annotations
 
@@ -32,6 +39,10 @@ def parse_args(argv=None):
     ap.add_argument("--uuid-names", action="store_true", help="Name simulation pods with uuid4s as the reference does.")
     ap.add_argument("--json", action="store_true", help="Print GetReport's review as JSON instead of the tables.")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--what-if-outage", default=None, metavar="KEY",
+                    help="After the report, schedule the queue once per outage: KEY = node (each node in turn) or a "
+                         "node label key (the nodes of each value in turn).")
+    ap.add_argument("--what-if-json", action="store_true", help="Print the what-if records as JSON.")
     return ap.parse_args(argv)
 
 
@@ -58,6 +69,9 @@ def main(argv=None) -> int:
         cc = scheduler.ClusterCapacity(nodes, running, sim, provider_name=a.algorithmprovider, policy_obj=pol,
                                        device=a.device)
         rep = cc.run()
+        what = None
+        if a.what_if_outage:
+            what = cc.what_if(scheduler.outage_sets(cc.cluster, a.what_if_outage))
     except Exception as e:  # glog.Fatalf("Failed to start scheduler simulator: %v", err)
         print("Failed to start scheduler simulator: %s" % e, file=sys.stderr)
         return 1
@@ -65,6 +79,13 @@ def main(argv=None) -> int:
         print(json.dumps(rep.review, default=_json_default, indent=1))
     else:
         sys.stdout.write(review_text(rep.review))
+    if what is not None:
+        if a.what_if_json:
+            print(json.dumps(what, default=_json_default, indent=1))
+        else:
+            for r in what:
+                print("what-if outage %s: nodes removed %d, scheduled %d, failed %d"
+                      % (r["name"], r["absent"], r["scheduled"], r["failed"]))
     return 0
 
 

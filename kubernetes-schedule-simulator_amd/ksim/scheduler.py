@@ -457,14 +457,23 @@ class GenericScheduler:
         self.last_stats = st
         return out, reasons, st
 
-    def sweep(self, scenarios, first=0, count=None):
+    def sweep(self, scenarios, first=0, count=None, absent=None):
         """Capacity-planning what-if (ksim_sweep): every scenario — a prioritizer list of map
         priorities, e.g. [("LeastRequestedPriority", 3), ("BalancedResourceAllocation", 1)] —
         schedules pods [first, first+count) on its own copy of the current node state, from the
         current lastNodeIndex, with this scheduler's predicates.  The scheduler's own state is
-        unchanged.  Returns (placements [n_scen][count], final counters [n_scen], stats)."""
+        unchanged.  Returns (placements [n_scen][count], final counters [n_scen], stats).
+
+        absent (ksim_sweep_nodes): one entry per scenario, an iterable of node indices or a
+        length-n bool array — the nodes that scenario's snapshot leaves out (node failure, zone
+        drain, scale-up candidates not bought).  They are not listed at all: never evaluated,
+        counted or selected, and the pods already on them are gone with them; placements stay
+        indices of the loaded table.  With absent, scenarios=None runs every scenario under this
+        scheduler's own policy.  self.last_scheduled then holds the pods bound per scenario."""
         n = len(self._pods)
         count = n - first if count is None else count
+        if absent is not None:
+            return self._sweep_nodes(scenarios, first, count, absent)
         w = np.zeros((len(scenarios), abi.NW), np.int64)
         for k, pri in enumerate(scenarios):
             cfg = make_config(self.predicates, pri)
@@ -476,6 +485,29 @@ class GenericScheduler:
         st = abi.Stats()
         self.h.call("ksim_sweep", abi.vptr(w), len(scenarios), first, count, abi.vptr(out), abi.vptr(ctr), C.byref(st))
         self.last_stats = st
+        return out, ctr, st
+
+    def _sweep_nodes(self, scenarios, first, count, absent):
+        mask = absent_mask(self.cluster.n_nodes, absent)
+        S = len(mask)
+        w = None
+        if scenarios is not None:
+            if len(scenarios) != S:
+                raise abi.KsimError(abi.E_INVAL, "sweep: %d scenarios but %d absent sets" % (len(scenarios), S))
+            w = np.zeros((S, abi.NW), np.int64)
+            for k, pri in enumerate(scenarios):
+                cfg = make_config(self.predicates, pri)
+                if cfg.no_priorities != self.cfg.no_priorities:
+                    raise Unsupported("a sweep scenario needs a non-empty prioritizer list like the scheduler's")
+                w[k] = list(cfg.weights)
+        out = np.zeros((S, count), np.int32)
+        ctr = np.zeros(S, np.uint64)
+        bound = np.zeros(S, np.int32)
+        st = abi.Stats()
+        self.h.call("ksim_sweep_nodes", abi.vptr(w), abi.vptr(mask), S, first, count, abi.vptr(out), abi.vptr(ctr),
+                    abi.vptr(bound), C.byref(st))
+        self.last_stats = st
+        self.last_scheduled = bound
         return out, ctr, st
 
     def evaluate(self, pod):
@@ -533,6 +565,57 @@ class GenericScheduler:
 
     def close(self):
         self.h.close()
+
+
+def absent_mask(n_nodes, sets):
+    """The node sets of ksim_sweep_nodes, packed: uint32 [len(sets)][ceil(n_nodes / 32)], bit
+    (j & 31) of word (j >> 5) set = node j (name rank) is absent in that scenario.  Each set is
+    an iterable of node indices or a length-n_nodes bool array; an index outside [0, n_nodes)
+    raises KsimError(E_INVAL)."""
+    n_nodes = int(n_nodes)
+    sets = list(sets)
+    words = (n_nodes + 31) // 32
+    out = np.zeros((len(sets), words), np.uint32)
+    for k, a in enumerate(sets):
+        a = np.asarray(a if isinstance(a, np.ndarray) else list(a))
+        if a.dtype == np.bool_:
+            if a.shape != (n_nodes,):
+                raise abi.KsimError(abi.E_INVAL, "absent set %d: a bool array must have one entry per node" % k)
+            idx = np.nonzero(a)[0]
+        elif a.size == 0:
+            continue
+        else:
+            if a.ndim != 1 or a.dtype.kind not in "iu":
+                raise abi.KsimError(abi.E_INVAL, "absent set %d: node indices must be integers" % k)
+            idx = a.astype(np.int64)
+            if idx.min() < 0 or idx.max() >= n_nodes:
+                raise abi.KsimError(abi.E_INVAL, "absent set %d: node index outside [0, %d)" % (k, n_nodes))
+        np.bitwise_or.at(out[k], idx >> 5, np.uint32(1) << (idx & 31).astype(np.uint32))
+    return out
+
+
+def outage_sets(cluster_or_nodes, by):
+    """The node sets of the usual outage what-ifs, as [(name, [node indices])] sorted by name.
+    by="node": one set per node, named after it; by=<label key>: one set per distinct value of
+    that node label, named after the value (nodes without the label are in no set).
+    cluster_or_nodes: a Cluster, or a list of v1.Node objects (indices are then their ranks in
+    bytewise name order, the order a Cluster built from them loads)."""
+    if isinstance(cluster_or_nodes, Cluster):
+        cl = cluster_or_nodes
+        names = list(cl.names) if cl.names else ["%d" % i for i in range(cl.n_nodes)]
+        sets_ = cl.label_sets.items
+        labels_ = [sets_[k] for k in np.asarray(cl.cols["label_set"])]
+    else:
+        nodes = sorted(cluster_or_nodes, key=lambda x: ((x.get("metadata") or {}).get("name", "")).encode())
+        names = [(x.get("metadata") or {}).get("name", "") for x in nodes]
+        labels_ = [(x.get("metadata") or {}).get("labels") or {} for x in nodes]
+    if by == "node":
+        return sorted(((nm, [i]) for i, nm in enumerate(names)), key=lambda t: t[0])
+    groups = {}
+    for i, lab in enumerate(labels_):
+        if by in lab:
+            groups.setdefault(lab[by], []).append(i)
+    return sorted(groups.items(), key=lambda t: t[0])
 
 
 class ShardedScheduler(GenericScheduler):
@@ -711,9 +794,10 @@ class ClusterCapacity:
                                             spread_services_only="ServiceSpreadingPriority" in names and not both,
                                             aux=aux if spread else None,
                                             service_affinity=svc_aff if "CheckServiceAffinity" in predicates else None)
-        self.scheduler = GenericScheduler(self.cluster, predicates, priorities, device=device, mode=mode,
-                                          collect_reasons=collect_reasons, label_presence=label_presence,
-                                          custom_priorities=custom, service_affinity=svc_aff)
+        self._sched_args = (predicates, priorities, dict(device=device, mode=mode, label_presence=label_presence,
+                                                         custom_priorities=custom, service_affinity=svc_aff))
+        self.scheduler = GenericScheduler(self.cluster, predicates, priorities, collect_reasons=collect_reasons,
+                                          **self._sched_args[2])
 
     def run(self) -> Report:
         from .report import ERR_NO_NODES, get_report, simulation_status
@@ -741,3 +825,42 @@ class ClusterCapacity:
         rep.stop_reason = rep.status.stop_reason
         rep.review = get_report(rep.status)
         return rep
+
+    def what_if(self, outages, first=0, count=None):
+        """Node-outage what-ifs over the snapshot (ksim_sweep_nodes): for every outage — (name, node
+        names or indices), or the output of outage_sets — the whole queue is scheduled on the
+        snapshot without those nodes, under the simulator's own provider or policy, all outages in
+        one sweep.  An absent node is not listed at all, and the running pods bound to it disappear
+        with it: nothing is re-queued.  The sweep starts from the snapshot as loaded (not from the
+        state a run() left), on a scheduler of its own.  Queues that are not resource-only are
+        refused (KsimUnsupported), as by GenericScheduler.sweep.
+        Returns one record per outage: dict(name, absent (node count), scheduled, failed,
+        placements [(pod name, node name or None)] in queue order)."""
+        cl = self.cluster
+        outages = list(outages)
+        sets_ = []
+        for name, members in outages:
+            idx = []
+            for m in members:
+                if isinstance(m, str):
+                    if m not in cl.index:
+                        raise abi.KsimError(abi.E_INVAL, "outage %r: no node named %r" % (name, m))
+                    m = cl.index[m]
+                idx.append(int(m))
+            sets_.append(sorted(set(idx)))
+        if not outages:
+            return []
+        predicates, priorities, kw = self._sched_args
+        g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
+        try:
+            out, _, _ = g.sweep(None, first, count, absent=sets_)
+        finally:
+            g.close()
+        names = cl.names
+        pod_names = cl.pod_names[first:first + out.shape[1]]
+        recs = []
+        for (name, _), idx, row in zip(outages, sets_, out):
+            bound = int((row >= 0).sum())
+            recs.append(dict(name=name, absent=len(idx), scheduled=bound, failed=len(row) - bound,
+                             placements=[(pn, names[w] if w >= 0 else None) for pn, w in zip(pod_names, row)]))
+        return recs
