@@ -314,9 +314,21 @@ int ksim_evaluate(ksim_handle* h, int64_t pod, uint8_t* out_fit, uint32_t* out_r
  * under their own map-priority weights (weights[s*KSIM_NW + KSIM_W_LEAST_REQUESTED /
  * _MOST_REQUESTED / _BALANCED]; the reduce slots must be 0), starting from the current
  * lastNodeIndex, with the configured predicates.  Replaces running the simulator once per
- * policy (pkg/scheduler/simulator.go:286 New, :187 Run).  Every pod must be resource-only;
- * the handle's own state is left unchanged.  out_node: [n_scen][count] node index or -1;
- * out_counters (optional): [n_scen] final lastNodeIndex. */
+ * policy (pkg/scheduler/simulator.go:286 New, :187 Run).  The handle's own state, counter and
+ * error word are left unchanged.  out_node: [n_scen][count] node index or -1; out_counters
+ * (optional): [n_scen] final lastNodeIndex.
+ * Pods: a range of resource-only pods takes the tree or scan form (at most 76,800 nodes, float64
+ * arithmetic: quantities that may reach 2^48 are refused).  Any other range takes the general form,
+ * exact int64, each scenario with its own copy of every column a commit writes: it accepts
+ * nodeName, host ports, node selectors / required node affinity, tolerations, gpu / ephemeral /
+ * extended requests, BestEffort pods and the svc_ok table form of CheckServiceAffinity, on at most
+ * 38,400 nodes (KSIM_SWEEP_GENERAL_MAX_NODES).  It refuses (KSIM_E_UNSUPPORTED, the reason in
+ * ksim_last_error) a pod in the range with inter-pod affinity, spread or volume state, loaded
+ * auxiliary-priority or CheckServiceAffinity lender tables, a pod class with more than
+ * KSIM_MAX_RCLASS reduce classes, a node-sharded handle, and scenario weights on a handle whose own
+ * policy has a reduce weight (TaintToleration, NodeAffinity) or a NodePreferAvoidPods addend: the
+ * scenario would drop that part of the policy (ksim_sweep_nodes with weights = NULL sweeps such a
+ * policy).  A scenario that overflows a node's host-port slots is a KSIM_E_OVERFLOW. */
 int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count,
                int32_t* out_node, uint64_t* out_counters, ksim_stats* stats);
 
@@ -331,9 +343,12 @@ int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t f
  * absent: [n_scen][ceil(n_nodes/32)] words, bit (j & 31) of word (j >> 5) set = node j (name rank)
  * is not listed in that scenario; bits at or above n_nodes are ignored; NULL = no node absent (then
  * identical to ksim_sweep).  weights: as ksim_sweep, or NULL = every scenario runs under the
- * handle's own configured weights (its reduce and constant priorities are one value on every node
- * for resource-only pods and drop out of the choice).  out_scheduled (optional): [n_scen] pods
- * bound.  Every refusal of ksim_sweep applies; the handle's own state is left unchanged. */
+ * handle's own configured policy: in the general form all of it (TaintToleration, NodeAffinity,
+ * the NodePreferAvoidPods addends, the constants); in the resource-only forms its reduce and
+ * constant priorities are one value on every node and drop out of the choice.  out_scheduled
+ * (optional): [n_scen] pods bound.  The accepted pods, the node caps (38,400 nodes in the general
+ * form) and every refusal are ksim_sweep's; a pod whose nodeName names an absent node fits nowhere
+ * in that scenario.  The handle's own state is left unchanged. */
 int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
                      int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters,
                      int32_t* out_scheduled, ksim_stats* stats);

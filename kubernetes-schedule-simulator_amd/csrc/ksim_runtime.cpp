@@ -1482,6 +1482,154 @@ static void sweep_scheduled(const int32_t* out_node, int32_t n_scen, int64_t cou
   }
 }
 
+// The general form of the sweep (ksim_sweep_general_kernel): a range with a pod that is not
+// resource-only.  Arguments as sweep_impl, which has checked them.
+static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
+                         int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
+                         ksim_stats* st) {
+  KsimCtx& c = h->ctx;
+  const int64_t n = c.n;
+  if (h->shard.world > 1) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a node-sharded handle sweeps resource-only pods only", who);
+  if (n > KSIM_SWEEP_GENERAL_MAX_NODES)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout of pods that are not "
+                                       "resource-only", who, (long long)n, KSIM_SWEEP_GENERAL_MAX_NODES);
+  if (ksim_rt_aff_count(h, first, count))
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state", who);
+  for (int64_t q = first; q < first + count; ++q)
+    if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: pod %lld mounts volumes", who, (long long)q);
+  if (ksim_rt_launch_tables(h))
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: an auxiliary spreading priority or CheckServiceAffinity's lender table is "
+                                       "loaded", who);
+  if (ksim_rt_range_wide(h, first, count))
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod class in the range has more than %d reduce classes", who,
+                KSIM_MAX_RCLASS);
+  if (weights && (c.w[KSIM_W_TAINT_TOLERATION] || c.w[KSIM_W_NODE_AFFINITY] || c.use_na))
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over pods that are not resource-only would drop the "
+                                       "handle's reduce priorities or NodePreferAvoidPods addend (weights = NULL sweeps "
+                                       "under the whole configured policy)", who);
+  std::vector<int64_t> w3(weights ? (size_t)n_scen * 3 : 0);
+  for (int32_t sidx = 0; sidx < (weights ? n_scen : 1); ++sidx) {
+    const int64_t* w = weights ? weights + (size_t)sidx * KSIM_NW : c.w;
+    if (weights && (w[KSIM_W_TAINT_TOLERATION] || w[KSIM_W_NODE_AFFINITY]))
+      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: reduce priorities are not swept", who, sidx);
+    // a packed evaluation holds the map score in KSIM_SWEEP_GENERAL_SCORE_BITS bits
+    int64_t tot = 0;
+    const int64_t lim = ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10;
+    for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED}) {
+      if (w[k] < 0 || w[k] >= lim) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
+      tot += w[k];
+    }
+    if (tot >= lim)
+      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: map scores exceed %d bits", who, sidx,
+                  KSIM_SWEEP_GENERAL_SCORE_BITS);
+    if (weights) {
+      w3[3 * (size_t)sidx] = w[KSIM_W_LEAST_REQUESTED];
+      w3[3 * (size_t)sidx + 1] = w[KSIM_W_MOST_REQUESTED];
+      w3[3 * (size_t)sidx + 2] = w[KSIM_W_BALANCED];
+    }
+  }
+  // scratch: a chunk of C scenarios' copies of every column a commit writes, their contexts and
+  // outputs, every scenario's weights and the sweep's error word.  The chunk follows the other
+  // forms' rule: at most 24 GiB and at most half of the device memory free now, halved while the
+  // allocation fails; one chunk is one launch.
+  const size_t S = (size_t)n_scen, N = (size_t)n, P = (size_t)count;
+  const size_t NS = (size_t)c.n_scalar, NP = (size_t)c.port_slots;
+  const int32_t aw = (int32_t)((n + 31) / 32);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
+  const size_t b_w = weights ? al(S * 24) : 0;
+  auto need_of = [&](size_t C) {
+    return 6 * al(C * N * 8) + 3 * al(C * N * 4) + al(C * N * NS * 8) + al(C * N * NP * 8) + al(C * sizeof(KsimCtx)) + b_w +
+           al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0);
+  };
+  size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
+  if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
+  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW;
+  int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
+  if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
+  if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
+    if (h->sw_scratch) {
+      for (auto& b : h->bufs)
+        if (b.p == h->sw_scratch) b.p = nullptr;
+      (void)hipFree(h->sw_scratch);
+      h->sw_scratch = nullptr;
+      h->sw_scratch_bytes = 0;
+    }
+    char* p = nullptr;
+    for (;;) {
+      const size_t need = need_of((size_t)chunk);
+      if (hipMalloc((void**)&p, need) == hipSuccess) {
+        h->bufs.push_back({p, need});
+        h->sw_scratch = p;
+        h->sw_scratch_bytes = need;
+        break;
+      }
+      (void)hipGetLastError();
+      if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "%s: no device memory for one scenario (%zu bytes)", who, need);
+      chunk = (chunk + 1) / 2;
+    }
+  }
+  const size_t C = (size_t)chunk;
+  char* q = (char*)h->sw_scratch;
+  auto take = [&](size_t b) { char* r = q; q += al(b); return r; };
+  SwgCols cols{};
+  cols.req_cpu = (int64_t*)take(C * N * 8); cols.req_mem = (int64_t*)take(C * N * 8);
+  cols.req_gpu = (int64_t*)take(C * N * 8); cols.req_eph = (int64_t*)take(C * N * 8);
+  cols.nz_cpu = (int64_t*)take(C * N * 8); cols.nz_mem = (int64_t*)take(C * N * 8);
+  cols.pod_count = (int32_t*)take(C * N * 4); cols.port_count = (int32_t*)take(C * N * 4);
+  cols.flags = (uint32_t*)take(C * N * 4);
+  cols.req_scalar = (int64_t*)take(C * N * NS * 8);
+  cols.ports = (uint64_t*)take(C * N * NP * 8);
+  SwgArgs a{};
+  a.n_pods = (int32_t)count;
+  a.first = first;
+  a.ctx = (KsimCtx*)take(C * sizeof(KsimCtx));
+  int64_t* dw = weights ? (int64_t*)take(S * 24) : nullptr;
+  a.w = dw;
+  a.out_node = (int32_t*)take(C * P * 4);
+  a.out_counter = (uint64_t*)take(C * 8);
+  int32_t* derr = (int32_t*)take(4);  // ksim_commit's port-slot overflow bit (the handle's word is not written)
+  uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
+  HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
+  if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
+  HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
+  float ms = 0.f;
+  for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
+    const int32_t nsc = std::min(chunk, n_scen - s0);
+    a.scen0 = s0;  // the chunk's first scenario: its row of the weights
+    if (absent)
+      HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
+    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h));
+    if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
+    HIPCHK(h, hipEventSynchronize(h->ev1));
+    float c_ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
+    ms += c_ms;
+    HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
+    if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
+  }
+  int32_t err = 0;
+  HIPCHK(h, hipMemcpy(&err, derr, 4, hipMemcpyDeviceToHost));
+  if (err)
+    return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's host-port slots overflowed in a scenario (load the node table with "
+                                    "more port slots)", who);
+  if (st) {
+    memset(st, 0, sizeof *st);
+    st->pods = (int64_t)(S * P);
+    int64_t b = 0;
+    for (size_t k = 0; k < S * P; ++k) b += out_node[k] >= 0;
+    st->scheduled = b;
+    st->node_evals = (int64_t)(S * P) * n;
+    st->device_ms = ms;
+    st->kernel_ms = ms;
+    st->kernel_launches = (n_scen + chunk - 1) / chunk;
+    st->mode = KSIM_MODE_PERSISTENT;
+    st->blocks = chunk;
+  }
+  sweep_scheduled(out_node, n_scen, count, out_scheduled);
+  return KSIM_OK;
+}
+
 // ksim_sweep (absent = NULL, weights given) and ksim_sweep_nodes.  absent: [n_scen][ceil(n / 32)]
 // words, a set bit = the node is not listed in that scenario; weights NULL = the handle's own.
 static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
@@ -1496,12 +1644,13 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
   const int64_t n = c.n;
   if (n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
   if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
+  // a pod that is not resource-only (ports, selectors, taints, nodeName, gpu / ephemeral / extended
+  // requests, more than one reduce class): the general form; else the forms below, as ever
+  if (h->fast_pre[first + count] - h->fast_pre[first] != count)
+    return sweep_general(h, who, weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled, st);
   if (n > KSIM_SWEEP_MAX_NODES)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout", who, (long long)n,
                 KSIM_SWEEP_MAX_NODES);
-  if (h->fast_pre[first + count] - h->fast_pre[first] != count)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: every pod must be resource-only (no ports, selectors, taints, "
-                                       "nodeName, gpu / ephemeral / extended requests)", who);
   std::vector<int32_t> w3((size_t)n_scen * 3);
   for (int32_t sidx = 0; sidx < n_scen; ++sidx) {
     // weights NULL: the handle's own map weights.  Its reduce and constant priorities are the same

@@ -27,3 +27,32 @@ struct SwArgs {
 };
 
 #define KSIM_SWEEP_MAX_NODES 76800  // uint16 evaluations of one scenario in LDS (150 KiB)
+
+// The general form (ksim_sweep_general_kernel): pods the resource-only forms do not take (host
+// ports, selectors, tolerations, nodeName, gpu / ephemeral / extended requests), evaluated in exact
+// int64 by the shared device code.  Scenario s of a chunk owns the s-th [n] slice of every column
+// a commit writes (SwgCols; [n_scalar][n] / [port_slots][n] of the scalar / port columns) and a
+// KsimCtx of its own: the handle's with those columns rebased and err at the sweep's own error word.
+struct SwgCols {
+  int64_t *req_cpu, *req_mem, *req_gpu, *req_eph, *nz_cpu, *nz_mem;
+  int64_t* req_scalar;
+  uint64_t* ports;
+  int32_t *pod_count, *port_count;
+  uint32_t* flags;
+};
+
+struct SwgArgs {
+  int32_t n_pods, scen0;
+  int64_t first;          // first pod of the range in KsimCtx::pods
+  const int64_t* w;       // [S][3] LeastRequested, MostRequested, BalancedResourceAllocation; null: the handle's own
+  uint64_t counter0;
+  KsimCtx* ctx;           // [C] the scenarios' contexts
+  int32_t* out_node;      // [C][n_pods]
+  uint64_t* out_counter;  // [C]
+};
+
+// one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
+#define KSIM_SWEEP_GENERAL_MAX_NODES 38400
+#define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word
+static_assert(KSIM_MAX_RCLASS <= 16, "the reduce class takes the low four bits of a packed evaluation");
+static_assert(sizeof(KsimCtx) + sizeof(SwgArgs) <= 4096 - 64, "KsimCtx + SwgArgs exceed the kernel-argument limit");

@@ -24,6 +24,12 @@
 // LDS, so F, M, C and the select prefix run over the listed nodes only, and a commit, which
 // lands on a fit row, never touches the bit.  Without a node set the ABS = false instantiation
 // runs.
+//
+// The general form (ksim_sweep_general_kernel, below the scan): the same shape for pods that are
+// not resource-only.  Every column a commit writes is the scenario's own, the evaluation is the
+// exact int64 one of the scheduling kernels (ksim_predicates_a, ksim_map_score, ksim_rclass_a), LDS
+// holds (map score << 4) | reduce class per node, and the pod's end is ksim_decide_lanes over the
+// per-class (max, count at max) of the workgroup.
 #include "ksim_decide.h"
 #include "ksim_sweep.h"
 #include "ksim_wave.h"
@@ -124,6 +130,233 @@ __global__ __launch_bounds__(SB) void ksim_sweep_kernel(SwArgs a) {
   if (tid == 0) a.out_counter[s] = counter;
 }
 
+// ---- the general form ----
+// Per pod:
+//   1. every thread evaluates rows j = tid, tid+1024, ...: a node the scenario does not list (sign
+//      bit of its pod count) is NOFIT before any predicate reads the count; ksim_predicates_a, then
+//      for a fit node ksim_map_score and ksim_rclass_a; the packed word goes to LDS.  With more than
+//      one reduce class the class's maximum is kept by an LDS atomic max (taken only by a score
+//      above the value read first); with one class (max, count) stay in registers as in the scan;
+//   2. F over the workgroup; per class the nodes at its maximum (one pass over the thread's
+//      contiguous LDS segment, one LDS atomic add per wave, step and class present);
+//   3. every wave runs ksim_decide_lanes over the classes (lane = class) -> winning classes and
+//      the nodes C at the best total; ix = lastNodeIndex % C when more than one node fits;
+//   4. the ix-th node from the top of the name order among the winning classes' nodes at their
+//      class maximum (the scan form's block prefix over contiguous segments); its thread commits
+//      with ksim_commit into the scenario's columns.
+// The per-class words are double-buffered by pod parity: the buffer of the next pod is reset
+// between two barriers of this one, so no reset races the next pod's atomics.
+namespace {
+constexpr uint32_t GNOFIT = 0xFFFFFFFFu;
+
+// The accessor of ksim_predicates_a / ksim_rclass_a (ksim_common.h, KsimGlobalAcc) with the pod
+// class's table entries of the node loaded together up front: the predicates return at the first
+// failure, so the global accessor's loads (set id, then table word, per predicate) would each wait
+// for the one before.
+struct SwgAcc {
+  const KsimCtx& c;
+  bool sel, tok, nok;
+  int ttc, nac;
+  __device__ __forceinline__ bool sel_ok(const ksim_pod&, int64_t) const { return sel; }
+  __device__ __forceinline__ bool taint_ok(const ksim_pod&, int64_t) const { return tok; }
+  __device__ __forceinline__ bool noexec_ok(const ksim_pod&, int64_t) const { return nok; }
+  __device__ __forceinline__ bool port_conflict(int64_t i, uint64_t want) const { return ksim_port_conflict(c, i, want); }
+  __device__ __forceinline__ uint64_t want(const ksim_pod& P, int32_t k) const { return ksim_pod_port(c, P, k); }
+  __device__ __forceinline__ int tt_class(const ksim_pod&, int64_t) const { return ttc; }
+  __device__ __forceinline__ int na_class(const ksim_pod&, int64_t) const { return nac; }
+};
+}  // namespace
+
+template <bool ABS>
+__global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* __restrict__ ctxs, const SwgArgs a) {
+  extern __shared__ uint32_t sg[];  // [n] evaluations of the current pod
+  __shared__ int32_t s_red[SW][3];
+  __shared__ int32_t s_wtot[SW];
+  __shared__ int32_t s_M[2][KSIM_MAX_RCLASS];  // max map score among the class's fit nodes (-1: none)
+  __shared__ int32_t s_C[2][KSIM_MAX_RCLASS];  // nodes at it
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int s = blockIdx.x;
+  // the scenario's context (ksim_sweep_general_ctx_kernel): read-only here, so its fields are
+  // uniform loads; a private modified copy of the kernel argument would live in scratch memory
+  // (the per-pod port / scalar arrays are indexed at run time)
+  const KsimCtx& c = ctxs[s];
+  const int64_t n = c.n;
+  const int64_t KS = (n + SB - 1) / SB;  // contiguous segment per thread in the count and select phases
+  const int64_t seg0 = (int64_t)tid * KS, seg1 = (seg0 + KS < n) ? seg0 + KS : n;
+  uint64_t counter = a.counter0;  // genericScheduler.lastNodeIndex of this scenario
+  if (tid < 2 * KSIM_MAX_RCLASS) {
+    (&s_M[0][0])[tid] = -1;
+    (&s_C[0][0])[tid] = 0;
+  }
+  __syncthreads();
+
+  for (int32_t p = 0; p < a.n_pods; ++p) {
+    const ksim_pod P = c.pods[a.first + p];
+    const int k1 = (c.w[KSIM_W_TAINT_TOLERATION] != 0) ? c.n_tt[P.cls] : 1;
+    const int k2 = c.use_na ? c.n_na[P.cls] : 1;
+    const int K = k1 * k2;  // <= KSIM_MAX_RCLASS (host-checked)
+    const int pb = p & 1;
+    const bool tabs = (P.flags & (KSIM_POD_NEED_SELECTOR | KSIM_POD_NEED_TAINTS)) || K > 1;
+    // the decision's per-class values, lane = class (loaded now, read after the evaluation)
+    int64_t tv = 0, av = 0, ad = 0;
+    if (K > 1 && lane < K) {
+      tv = c.tt_val[(int64_t)P.cls * c.val_w + lane / k2];
+      av = c.na_val[(int64_t)P.cls * c.val_w + lane % k2];
+      ad = c.na_add ? c.na_add[(int64_t)P.cls * c.val_w + lane % k2] : 0;
+    }
+    // ---- 1. evaluate every row ----
+    int32_t f = 0, mx = -1, cm = 0;
+    for (int64_t j = tid; j < n; j += SB) {
+      const KsimRow r = ksim_load_row(c, j);
+      SwgAcc acc{c, true, true, true, 0, 0};
+      if (tabs) {  // uniform: the pod reads a class table
+        const int64_t cl = P.cls;
+        const int32_t ls = c.label_set[j], ts = c.taint_set[j];
+        if (P.flags & KSIM_POD_NEED_SELECTOR) acc.sel = ksim_bit(c.sel_ok, cl, c.lwords, ls);
+        if (P.flags & KSIM_POD_NEED_TAINTS) {
+          acc.tok = ksim_bit(c.taint_ok, cl, c.twords, ts);
+          acc.nok = ksim_bit(c.noexec_ok, cl, c.twords, ts);
+        }
+        if (k1 > 1) acc.ttc = c.tt_class[cl * c.n_taint_sets + ts];
+        if (k2 > 1) acc.nac = c.na_class[cl * c.n_label_sets + ls];
+      }
+      bool fit = true;
+      if constexpr (ABS) fit = r.count >= 0;  // a node this scenario does not list
+      if (fit) fit = ksim_predicates_a<SwgAcc, true, true>(c, P, j, r, acc) == 0;
+      uint32_t wd = GNOFIT;
+      if (fit) {
+        const int32_t e = (int32_t)ksim_map_score(c, P, r);  // < 2^27 (host-checked weights)
+        int q = 0;
+        if (K > 1) {
+          q = ksim_rclass_a(P, j, k1, k2, acc);
+          if (e > __hip_atomic_load(&s_M[pb][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&s_M[pb][q], e);
+        }
+        wd = ((uint32_t)e << 4) | (uint32_t)q;
+        f += 1;
+        cm = e > mx ? 1 : cm + (e == mx ? 1 : 0);
+        mx = e > mx ? e : mx;
+      }
+      sg[j] = wd;
+    }
+    // ---- 2. block reduction: F, and for one class M, C ----
+    {
+      const int32_t Fw = ksimw::sum_i32(f);
+      const int32_t Mw = ksimw::max_i32(mx);
+      const int32_t Cw = ksimw::sum_i32((mx == Mw && mx >= 0) ? cm : 0);
+      if (lane == 0) { s_red[wv][0] = Fw; s_red[wv][1] = Mw; s_red[wv][2] = Cw; }
+    }
+    __syncthreads();
+    if (tid < KSIM_MAX_RCLASS) {  // the next pod's class words
+      s_M[pb ^ 1][tid] = -1;
+      s_C[pb ^ 1][tid] = 0;
+    }
+    const bool in = lane < SW;
+    const int32_t F = ksimw::sum_i32(in ? s_red[in ? lane : 0][0] : 0);
+    const int32_t mw = in ? s_red[lane][1] : -1;
+    const int32_t M = ksimw::max_i32(mw);
+    int32_t C = ksimw::sum_i32((in && mw == M && M >= 0) ? s_red[lane][2] : 0);
+    if (F == 0) {  // FitError: no node fits
+      if (tid == 0) a.out_node[(int64_t)s * a.n_pods + p] = -1;
+      __syncthreads();  // s_red is rewritten by the next pod
+      continue;
+    }
+    uint32_t win = 1u;
+    if (K > 1) {
+      // nodes at their class's maximum, per class
+      for (int64_t k = 0; k < KS; ++k) {
+        const int64_t j = seg0 + k;
+        const uint32_t wd = j < seg1 ? sg[j] : GNOFIT;
+        const uint32_t q = wd & 15u;
+        const bool cand = wd != GNOFIT && (int32_t)(wd >> 4) == s_M[pb][q];
+        uint64_t m = __ballot(cand);
+        while (m) {  // uniform: one step per class present among the wave's candidates
+          const int l = __builtin_ctzll(m);
+          const uint32_t ql = (uint32_t)__builtin_amdgcn_readlane((int)q, l);
+          const uint64_t same = __ballot(cand && q == ql);
+          if (lane == l) atomicAdd(&s_C[pb][ql], (int32_t)__popcll(same));
+          m &= ~same;
+        }
+      }
+      __syncthreads();
+      // ---- 3. the winning classes (every wave decides; lane = class) ----
+      const int lq = lane & (KSIM_MAX_RCLASS - 1);
+      const int32_t Cq = s_C[pb][lq];
+      const bool live = lane < K && Cq > 0;
+      uint64_t wb;
+      int64_t best;
+      C = ksim_decide_lanes<KsimReduceWave>(c, live, (int64_t)s_M[pb][lq], live ? Cq : 0, tv, av, ad, wb, best);
+      win = (uint32_t)wb;
+    }
+    const uint32_t ix = (F > 1) ? (uint32_t)ksim_select_ix(counter, (uint32_t)C) : 0u;
+    counter += (F > 1) ? 1 : 0;  // generic_scheduler.go:192-195 (selectHost only when F > 1)
+    // ---- 4. the ix-th node at the best total from the top ----
+    const uint32_t one_word = (uint32_t)M << 4;
+    auto at_best = [&](uint32_t wd) -> bool {
+      if (K == 1) return wd == one_word;
+      return wd != GNOFIT && ((win >> (wd & 15u)) & 1u) && (int32_t)(wd >> 4) == s_M[pb][wd & 15u];
+    };
+    int32_t c_t = 0;
+    for (int64_t j = seg0; j < seg1; ++j) c_t += at_best(sg[j]) ? 1 : 0;
+    const int32_t pre = ksimw::prefix_incl_i32(c_t);  // within the wave
+    if (lane == 63) s_wtot[wv] = pre;
+    __syncthreads();
+    int32_t below = 0;  // matches in lower waves
+    for (int w = 0; w < SW; ++w) below += (w < wv) ? s_wtot[w] : 0;
+    const uint32_t above = (uint32_t)(C - (below + pre));  // matches in higher threads
+    if (c_t > 0 && ix >= above && ix < above + (uint32_t)c_t) {
+      int32_t r = (int32_t)(ix - above);
+      int64_t jsel = -1;
+      for (int64_t j = seg1 - 1; j >= seg0; --j) {
+        if (at_best(sg[j])) {
+          if (r == 0) { jsel = j; break; }
+          --r;
+        }
+      }
+      if (jsel >= 0) ksim_commit(c, P, jsel);
+      a.out_node[(int64_t)s * a.n_pods + p] = (int32_t)jsel;
+    }
+    __syncthreads();  // the commit (workgroup release/acquire) before the next pod's loads
+  }
+  if (tid == 0) a.out_counter[s] = counter;
+}
+
+// Scenario s of the chunk gets its context: k (the handle's, its dynamic columns at the chunk's
+// first copy, err at the sweep's own word) rebased to the scenario's copies, nothing of the per-pod,
+// affinity, volume or sharded forms, and the scenario's map weights when weights are given.
+__global__ void ksim_sweep_general_ctx_kernel(const KsimCtx k, const int64_t* w, int32_t scen0, int32_t n_scen,
+                                              KsimCtx* out) {
+  const int32_t s = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (s >= n_scen) return;
+  KsimCtx& c = out[s];
+  c = k;
+  const int64_t off = (int64_t)s * k.n;
+  c.req_cpu = k.req_cpu + off; c.req_mem = k.req_mem + off; c.req_gpu = k.req_gpu + off; c.req_eph = k.req_eph + off;
+  c.nz_cpu = k.nz_cpu + off; c.nz_mem = k.nz_mem + off;
+  c.pod_count = k.pod_count + off; c.port_count = k.port_count + off; c.flags = k.flags + off;
+  c.req_scalar = k.req_scalar + off * k.n_scalar;
+  c.ports = k.ports + off * k.port_slots;
+  c.one = 0; c.aff = nullptr; c.vol = nullptr; c.collect = 0; c.no_commit = 0; c.sh_world = 0;
+  if (w) {
+    const int64_t* ws = w + 3 * (int64_t)(scen0 + s);
+    c.w[KSIM_W_LEAST_REQUESTED] = ws[0];
+    c.w[KSIM_W_MOST_REQUESTED] = ws[1];
+    c.w[KSIM_W_BALANCED] = ws[2];
+  }
+}
+
+// every scenario's copy of the columns a commit writes, from the handle's current node state
+__global__ void ksim_sweep_general_init_kernel(SwgCols src, SwgCols d, int64_t n, int32_t n_scalar, int32_t port_slots,
+                                               int64_t total) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= total) return;
+  const int64_t i = k % n, s = k / n;
+  d.req_cpu[k] = src.req_cpu[i]; d.req_mem[k] = src.req_mem[i]; d.req_gpu[k] = src.req_gpu[i];
+  d.req_eph[k] = src.req_eph[i]; d.nz_cpu[k] = src.nz_cpu[i]; d.nz_mem[k] = src.nz_mem[i];
+  d.pod_count[k] = src.pod_count[i]; d.port_count[k] = src.port_count[i]; d.flags[k] = src.flags[i];
+  for (int32_t t = 0; t < n_scalar; ++t) d.req_scalar[(s * n_scalar + t) * n + i] = src.req_scalar[(int64_t)t * n + i];
+  for (int32_t t = 0; t < port_slots; ++t) d.ports[(s * port_slots + t) * n + i] = src.ports[(int64_t)t * n + i];
+}
+
 // static float64 columns, once per handle
 __global__ void ksim_sweep_static_kernel(const int64_t* ac, const int64_t* am, int64_t n, double* dac, double* dam,
                                          double* yc, double* ym) {
@@ -187,6 +420,41 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
     hipLaunchKernelGGL(ksim_sweep_kernel<true>, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
   else
     hipLaunchKernelGGL(ksim_sweep_kernel<false>, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
+  e = hipGetLastError();
+  if (ev1) (void)hipEventRecord(ev1, st);
+  return e;
+}
+
+// The general form: hc the handle's context, cols the chunk's scenario columns, err the sweep's own
+// error word (ksim_commit's port-slot overflow bit; the handle's word is never written).
+extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgs* args,
+                                                int32_t n_scen, const uint32_t* absent, int32_t absent_words,
+                                                int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
+  const int64_t n = hc->n, total = n * (int64_t)n_scen;
+  SwgCols src{hc->req_cpu, hc->req_mem, hc->req_gpu, hc->req_eph, hc->nz_cpu, hc->nz_mem,
+              hc->req_scalar, hc->ports, hc->pod_count, hc->port_count, hc->flags};
+  hipLaunchKernelGGL(ksim_sweep_general_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, *cols, n,
+                     hc->n_scalar, hc->port_slots, total);
+  if (absent)
+    hipLaunchKernelGGL(ksim_sweep_absent_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, absent,
+                       absent_words, n, total, cols->pod_count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (ev0) (void)hipEventRecord(ev0, st);
+  KsimCtx k = *hc;
+  k.req_cpu = cols->req_cpu; k.req_mem = cols->req_mem; k.req_gpu = cols->req_gpu; k.req_eph = cols->req_eph;
+  k.nz_cpu = cols->nz_cpu; k.nz_mem = cols->nz_mem; k.req_scalar = cols->req_scalar; k.ports = cols->ports;
+  k.pod_count = cols->pod_count; k.port_count = cols->port_count; k.flags = cols->flags;
+  k.err = err;
+  hipLaunchKernelGGL(ksim_sweep_general_ctx_kernel, dim3((unsigned)((n_scen + 63) / 64)), dim3(64), 0, st, k, args->w,
+                     args->scen0, n_scen, args->ctx);
+  const size_t lds = (size_t)n * sizeof(uint32_t);
+  if (absent)
+    hipLaunchKernelGGL(ksim_sweep_general_kernel<true>, dim3((unsigned)n_scen), dim3(SB), lds, st,
+                       (const KsimCtx*)args->ctx, *args);
+  else
+    hipLaunchKernelGGL(ksim_sweep_general_kernel<false>, dim3((unsigned)n_scen), dim3(SB), lds, st,
+                       (const KsimCtx*)args->ctx, *args);
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;

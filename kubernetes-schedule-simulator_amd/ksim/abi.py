@@ -18,6 +18,8 @@ ABI_VERSION = 7
 MAX_SCALAR = 8
 MAX_RCLASS = 16
 MAX_WIDE = 256  # reduce classes per pod (KSIM_MAX_WIDE)
+# node cap of the scenario sweep's general form (KSIM_SWEEP_GENERAL_MAX_NODES, csrc/ksim_sweep.h)
+SWEEP_GENERAL_MAX_NODES = 38400
 NREASONS = 32
 
 # predicate bits

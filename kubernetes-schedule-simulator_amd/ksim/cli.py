@@ -17,7 +17,9 @@ is, like anaCheckPoint).  Exit status 1 with a message on every error, like glog
 (ClusterCapacity.what_if): KEY = node removes each node in turn (N-1), any other KEY removes the
 nodes of each value of that node label in turn (a zone or rack drain).  One line per outage with
 its name, the nodes removed and the pods scheduled and failed; --what-if-json prints the records
-as JSON instead.
+as JSON instead.  Snapshots and podspecs with node selectors, tolerations, host ports, nodeName
+and extended resources are swept under the whole provider or policy; inter-pod affinity, spread
+listers and volumes are refused there (the normal report is printed first either way).
 """
 from __future__ import annotations
 

@@ -469,7 +469,19 @@ class GenericScheduler:
         drain, scale-up candidates not bought).  They are not listed at all: never evaluated,
         counted or selected, and the pods already on them are gone with them; placements stay
         indices of the loaded table.  With absent, scenarios=None runs every scenario under this
-        scheduler's own policy.  self.last_scheduled then holds the pods bound per scenario."""
+        scheduler's own policy.  self.last_scheduled then holds the pods bound per scenario.
+
+        Queues: resource-only pods take the tree or scan form.  Any other range is swept by the
+        general form (stats.mode == MODE_PERSISTENT, exact int64, at most
+        abi.SWEEP_GENERAL_MAX_NODES nodes): pods with nodeName, host ports, node selectors /
+        required node affinity, tolerations, gpu / ephemeral / extended requests, BestEffort pods,
+        and with scenarios=None the whole configured policy (TaintToleration, NodeAffinity,
+        NodePreferAvoidPods, the constants).  Still refused (KsimUnsupported): a pod in the range
+        with inter-pod affinity, spread or volume state, an auxiliary spreading priority or
+        CheckServiceAffinity with services selecting the pods, more than abi.MAX_RCLASS reduce
+        classes in a pod class, a node-sharded scheduler, a scenario with a reduce priority, and
+        explicit scenarios over such a queue when this scheduler's own policy has a reduce
+        priority or a NodePreferAvoidPods addend (pass scenarios=None with absent sets)."""
         n = len(self._pods)
         count = n - first if count is None else count
         if absent is not None:
@@ -832,8 +844,10 @@ class ClusterCapacity:
         snapshot without those nodes, under the simulator's own provider or policy, all outages in
         one sweep.  An absent node is not listed at all, and the running pods bound to it disappear
         with it: nothing is re-queued.  The sweep starts from the snapshot as loaded (not from the
-        state a run() left), on a scheduler of its own.  Queues that are not resource-only are
-        refused (KsimUnsupported), as by GenericScheduler.sweep.
+        state a run() left), on a scheduler of its own.  Queues with node selectors, tolerations,
+        host ports, nodeName and gpu / ephemeral / extended requests are swept under the whole
+        provider or policy; queues with inter-pod affinity, spread or volume state are refused
+        (KsimUnsupported), as by GenericScheduler.sweep.
         Returns one record per outage: dict(name, absent (node count), scheduled, failed,
         placements [(pod name, node name or None)] in queue order)."""
         cl = self.cluster
