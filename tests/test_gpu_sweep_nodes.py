@@ -175,6 +175,41 @@ def test_absent_sets_ragged_tail_and_deeper_tree(n, p, form, monkeypatch):
     g.close()
 
 
+SCAN_MAX_NODES = 76_800  # KSIM_SWEEP_MAX_NODES: one uint16 evaluation per node in 150 KiB of dynamic LDS
+
+
+def test_scan_form_at_its_node_cap(monkeypatch):
+    """76,800 nodes: 150 KiB of dynamic LDS per workgroup, 75-row select segments."""
+    assert SCAN_MAX_NODES * 2 == 150 * 1024
+    monkeypatch.setenv("KSIM_SWEEP_SCAN", "1")
+    cl, scen, refs = _ragged_case(SCAN_MAX_NODES, 300)
+    g = scheduler.GenericScheduler(cl, PREDS, POLICIES[0], collect_reasons=False)
+    before = g.node_state()
+    out, ctr, st = g.sweep([pri for _, _, pri in scen], 0, len(cl.pods), absent=[a for _, a, _ in scen])
+    assert st.mode == abi.MODE_PERSISTENT
+    assert st.kernel_launches == 1 and st.blocks == len(scen) == 3
+    _check(scen, refs, out, ctr, g.last_scheduled, cl.n_nodes)
+    assert not np.array_equal(out[0], out[1]) and not np.array_equal(out[0], out[2])
+    after = g.node_state()
+    for key in before:
+        assert np.array_equal(before[key], after[key]), key
+    assert g.last_node_index == 0
+    g.close()
+
+
+@pytest.mark.parametrize("form", ["tree", "scan"])
+def test_one_node_beyond_the_cap_is_refused(form, monkeypatch):
+    _sweep_form(form, monkeypatch)
+    cl = _cluster(SCAN_MAX_NODES + 1, 20)
+    g = scheduler.GenericScheduler(cl, PREDS, POLICIES[0], collect_reasons=False)
+    with pytest.raises(abi.KsimUnsupported, match="76800"):
+        g.sweep(POLICIES, 0, 20, absent=[[], [0]])
+    with pytest.raises(abi.KsimUnsupported, match="76800"):
+        g.sweep(POLICIES, 0, 20)
+    assert g.last_node_index == 0
+    g.close()
+
+
 @pytest.mark.parametrize("form", SWEEP_FORMS)
 def test_empty_sets_equal_the_plain_sweep(form, monkeypatch):
     _sweep_form(form, monkeypatch)

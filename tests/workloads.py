@@ -405,3 +405,53 @@ def rnd_svc_affinity_workload(seed, n_nodes=24, n_pods=120, mixed_labels=False, 
                 {"metadata": md("ns1"), "spec": {"selector": {"app": "b"}}},
                 {"metadata": md("ns2"), "spec": {"selector": {"app": "a"}}}]
     return nodes, running, pods, services
+
+
+# ----------------------------------------------------------------------------- scenario sweep edges
+def _uniform_node(name, labels, taints=()):
+    node = {"metadata": {"name": name, "labels": dict(labels)}, "spec": {},
+            "status": {"allocatable": {"cpu": "8", "memory": "16Gi", "pods": "110"},
+                       "conditions": [{"type": "Ready", "status": "True"}]}}
+    if taints:
+        node["spec"]["taints"] = [{"key": k, "value": "true", "effect": "PreferNoSchedule"} for k in taints]
+    return node
+
+
+def uniform_selector_workload(n, p, taint_every=0, cpu="500m", mem="1Gi"):
+    """A uniform cluster whose pods tie on every node that fits: n nodes u-00000.. (name order =
+    index order; 8 cpu, 16Gi, 110 pods, pool=a) and p identical pods with nodeSelector pool=a, so
+    the nodes at the best total start as every fit node and shrink by one per pod.  Nodes 0, n//2
+    and n-1 are pool=b decoys: the pods carry POD_NEED_SELECTOR (not resource-only) and the
+    selector fails at the first, a middle and the last node.  taint_every=2: odd nodes carry one
+    PreferNoSchedule taint no pod tolerates (two TaintToleration classes).  Returns (nodes, pods)
+    with pods in scheduling order."""
+    decoys = {0, n // 2, n - 1}
+    nodes = []
+    for i in range(n):
+        taints = ("spot",) if taint_every and i % taint_every == taint_every - 1 else ()
+        nodes.append(_uniform_node("u-%05d" % i, {"pool": "b" if i in decoys else "a"}, taints))
+    pods = [{"metadata": {"name": "u-pod-%d" % k, "namespace": "default"},
+             "spec": {"containers": [{"resources": {"requests": {"cpu": cpu, "memory": mem}}}],
+                      "nodeSelector": {"pool": "a"}}} for k in range(p)]
+    return nodes, pods
+
+
+def sixteen_class_workload(n=203, kt=4):
+    """kt x 4 reduce classes for every pod: node i (k-00000.., 8 cpu, 16Gi) carries i % kt distinct
+    PreferNoSchedule taints (TaintToleration classes 0..kt-1) and the label tier=t{(i // kt) % 4},
+    which the pods' preferred node affinity weighs 0 / 10 / 20 / 30 (four NodeAffinity classes);
+    nodes 0 and n-1 are pool=b decoys of the pods' pool=a selector.  4n + 7 pods of cpu 2 / 4Gi
+    (four a node) fill every (taints, tier) pair and overflow the cluster.  kt=4 is exactly
+    KSIM_MAX_RCLASS, kt=5 is beyond it.  Returns (nodes, pods) with pods in scheduling order."""
+    nodes = []
+    for i in range(n):
+        labels = {"pool": "b" if i in (0, n - 1) else "a", "tier": "t%d" % ((i // kt) % 4)}
+        nodes.append(_uniform_node("k-%05d" % i, labels, ["taint-%d" % t for t in range(i % kt)]))
+    prefer = [{"weight": w, "preference": {"matchExpressions": [{"key": "tier", "operator": "In", "values": [t]}]}}
+              for w, t in ((10, "t1"), (20, "t2"), (30, "t3"))]
+    pods = [{"metadata": {"name": "k-pod-%d" % k, "namespace": "default"},
+             "spec": {"containers": [{"resources": {"requests": {"cpu": "2", "memory": "4Gi"}}}],
+                      "nodeSelector": {"pool": "a"},
+                      "affinity": {"nodeAffinity": {"preferredDuringSchedulingIgnoredDuringExecution": prefer}}}}
+            for k in range(4 * n + 7)]
+    return nodes, pods
