@@ -41,10 +41,10 @@ extern "C" size_t ksim_persistent_granule_bytes(int grid);
 extern "C" hipError_t ksim_sweep_prepare(const int64_t* ac, const int64_t* am, int64_t n, double* dac, double* dam,
                                          double* yc, double* ym, hipStream_t st);
 extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, const int64_t* zc0, const int64_t* zm0,
-                                        const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgs* args,
+                                        const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgsWhy* args,
                                         int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
                                         hipEvent_t ev1, hipStream_t st);
-extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgs* args,
+extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsWhy* args,
                                                 int32_t n_scen, const uint32_t* absent, int32_t absent_words,
                                                 int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
 extern "C" int ksim_pfast_config(int64_t n, int max_grid, int stream, int* grid, int* lds_rows);

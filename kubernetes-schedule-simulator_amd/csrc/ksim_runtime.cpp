@@ -1,10 +1,13 @@
-// ksim_runtime.cpp — host side of libksim.so: the C-ABI declared in include/ksim.h.
+// ksim_runtime.cpp — host side of libksim.so: the C-ABI declared in include/ksim.h and
+// include/ksim_whatif.h.
 //
 // Owns the device-resident node table (SoA columns in HBM), the pod-class tables, the
 // pod queue and the run state, and drives the scan kernels on one HIP stream per handle.
 // No torch types cross this boundary; every entry point calls hipSetDevice (cgo calls may
 // land on any OS thread) and returns a KSIM_* status.
 #include "ksim_handle.h"
+
+#include "../../include/ksim_whatif.h"
 
 namespace {
 thread_local std::string g_err;
@@ -1482,13 +1485,87 @@ static void sweep_scheduled(const int32_t* out_node, int32_t n_scen, int64_t cou
   }
 }
 
+// ---- ksim_sweep_explain (include/ksim_whatif.h): the failed pods' records ----
+// Records a scenario keeps on the device: none without a record array, and never more than the
+// range has pods.
+static int32_t why_cap(const ksim_sweep_failures* fail, int64_t count) {
+  return fail && fail->cap > 0 ? (int32_t)std::min<int64_t>(fail->cap, count) : 0;
+}
+// device bytes of one scenario's records: [cap] pod indices + [cap][KSIM_NREASONS] histograms
+static size_t why_bytes(int32_t cap) { return (size_t)cap * (1 + KSIM_NREASONS) * 4; }
+
+// A chunk's records ([nsc][cap] pods, [nsc][cap][KSIM_NREASONS] histograms on the device) into the
+// caller's arrays at the chunk's scenario offset s0: per scenario the first min(failed, cap), the
+// words past them left unwritten.  out_node: the chunk's placements, already on the host.
+static int why_copy_out(ksim_handle* h, const ksim_sweep_failures* fail, int32_t cap, int32_t s0, int32_t nsc,
+                        int64_t count, const int32_t* out_node, const int32_t* dpod, const int32_t* dhist) {
+  if (!cap) return KSIM_OK;
+  std::vector<int32_t> kept((size_t)nsc);
+  size_t total = 0;
+  for (int32_t s = 0; s < nsc; ++s) {
+    int64_t nf = 0;
+    for (int64_t k = 0; k < count; ++k) nf += out_node[(size_t)s * count + k] < 0;
+    kept[s] = (int32_t)std::min<int64_t>(nf, cap);
+    total += (size_t)kept[s];
+  }
+  if (!total) return KSIM_OK;
+  const size_t ucap = (size_t)fail->cap;  // the caller's stride
+  // few kept records in a large chunk: one copy per scenario; else the chunk's arrays in one go
+  const bool whole = total * 4 >= (size_t)nsc * cap || (size_t)nsc * why_bytes(cap) <= ((size_t)8 << 20);
+  std::vector<int32_t> hp, hh;
+  if (whole) {
+    hp.resize((size_t)nsc * cap);
+    hh.resize((size_t)nsc * cap * KSIM_NREASONS);
+    HIPCHK(h, hipMemcpy(hp.data(), dpod, hp.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(hh.data(), dhist, hh.size() * 4, hipMemcpyDeviceToHost));
+  }
+  for (int32_t s = 0; s < nsc; ++s) {
+    const size_t k = (size_t)kept[s];
+    if (!k) continue;
+    int32_t* up = fail->pod + (size_t)(s0 + s) * ucap;
+    int32_t* uh = fail->hist + (size_t)(s0 + s) * ucap * KSIM_NREASONS;
+    if (whole) {
+      memcpy(up, hp.data() + (size_t)s * cap, k * 4);
+      memcpy(uh, hh.data() + (size_t)s * cap * KSIM_NREASONS, k * KSIM_NREASONS * 4);
+    } else {
+      HIPCHK(h, hipMemcpy(up, dpod + (size_t)s * cap, k * 4, hipMemcpyDeviceToHost));
+      HIPCHK(h, hipMemcpy(uh, dhist + (size_t)s * cap * KSIM_NREASONS, k * KSIM_NREASONS * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  return KSIM_OK;
+}
+
+// count[s] = failed pods, listed[s] = n - |absent set of s| (bits at or above n ignored)
+static void why_counts(const ksim_sweep_failures* fail, const uint32_t* absent, int64_t n, int32_t n_scen, int64_t count,
+                       const int32_t* out_node) {
+  if (!fail) return;
+  const int32_t aw = (int32_t)((n + 31) / 32);
+  for (int32_t s = 0; s < n_scen; ++s) {
+    if (fail->count) {
+      int32_t nf = 0;
+      for (int64_t k = 0; k < count; ++k) nf += out_node[(size_t)s * count + k] < 0;
+      fail->count[s] = nf;
+    }
+    if (fail->listed) {
+      int64_t gone = 0;
+      for (int32_t w = 0; absent && w < aw; ++w) {
+        uint32_t m = absent[(size_t)s * aw + w];
+        if (w == aw - 1 && (n & 31)) m &= (1u << (n & 31)) - 1u;
+        gone += __builtin_popcount(m);
+      }
+      fail->listed[s] = (int32_t)(n - gone);
+    }
+  }
+}
+
 // The general form of the sweep (ksim_sweep_general_kernel): a range with a pod that is not
 // resource-only.  Arguments as sweep_impl, which has checked them.
 static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
                          int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                         ksim_stats* st) {
+                         const ksim_sweep_failures* fail, ksim_stats* st) {
   KsimCtx& c = h->ctx;
   const int64_t n = c.n;
+  const int32_t wcap = why_cap(fail, count);
   if (h->shard.world > 1) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a node-sharded handle sweeps resource-only pods only", who);
   if (n > KSIM_SWEEP_GENERAL_MAX_NODES)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout of pods that are not "
@@ -1540,11 +1617,11 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   const size_t b_w = weights ? al(S * 24) : 0;
   auto need_of = [&](size_t C) {
     return 6 * al(C * N * 8) + 3 * al(C * N * 4) + al(C * N * NS * 8) + al(C * N * NP * 8) + al(C * sizeof(KsimCtx)) + b_w +
-           al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0);
+           al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0) + (wcap ? al(C * wcap * 4) + al(C * why_bytes(wcap) - C * wcap * 4) : 0);
   };
   size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
   if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
-  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW;
+  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW + why_bytes(wcap);
   int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
   if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
   if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
@@ -1580,7 +1657,7 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   cols.flags = (uint32_t*)take(C * N * 4);
   cols.req_scalar = (int64_t*)take(C * N * NS * 8);
   cols.ports = (uint64_t*)take(C * N * NP * 8);
-  SwgArgs a{};
+  SwgArgsWhy a{};
   a.n_pods = (int32_t)count;
   a.first = first;
   a.ctx = (KsimCtx*)take(C * sizeof(KsimCtx));
@@ -1590,6 +1667,11 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   a.out_counter = (uint64_t*)take(C * 8);
   int32_t* derr = (int32_t*)take(4);  // ksim_commit's port-slot overflow bit (the handle's word is not written)
   uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
+  if (wcap) {  // the chunk's records of failed pods (ksim_sweep_explain)
+    a.why.cap = wcap;
+    a.why.pod = (int32_t*)take(C * wcap * 4);
+    a.why.hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
+  }
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
@@ -1607,6 +1689,7 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     ms += c_ms;
     HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
     if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
+    if (int rcw = why_copy_out(h, fail, wcap, s0, nsc, count, out_node + (size_t)s0 * P, a.why.pod, a.why.hist)) return rcw;
   }
   int32_t err = 0;
   HIPCHK(h, hipMemcpy(&err, derr, 4, hipMemcpyDeviceToHost));
@@ -1627,14 +1710,15 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     st->blocks = chunk;
   }
   sweep_scheduled(out_node, n_scen, count, out_scheduled);
+  why_counts(fail, absent, n, n_scen, count, out_node);
   return KSIM_OK;
 }
 
-// ksim_sweep (absent = NULL, weights given) and ksim_sweep_nodes.  absent: [n_scen][ceil(n / 32)]
+// ksim_sweep (absent = NULL, weights given), ksim_sweep_nodes and ksim_sweep_explain (fail).  absent: [n_scen][ceil(n / 32)]
 // words, a set bit = the node is not listed in that scenario; weights NULL = the handle's own.
 static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
                       int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                      ksim_stats* st) {
+                      const ksim_sweep_failures* fail, ksim_stats* st) {
   if (!h || !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
   if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
   if (n_scen <= 0 || first < 0 || count <= 0 || first + count > h->n_pods || count > INT32_MAX)
@@ -1647,7 +1731,7 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
   // a pod that is not resource-only (ports, selectors, taints, nodeName, gpu / ephemeral / extended
   // requests, more than one reduce class): the general form; else the forms below, as ever
   if (h->fast_pre[first + count] - h->fast_pre[first] != count)
-    return sweep_general(h, who, weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled, st);
+    return sweep_general(h, who, weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st);
   if (n > KSIM_SWEEP_MAX_NODES)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout", who, (long long)n,
                 KSIM_SWEEP_MAX_NODES);
@@ -1685,6 +1769,7 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
   }
   int rc;
   const int32_t aw = (int32_t)((n + 31) / 32);  // node-set words per scenario
+  const int32_t wcap = why_cap(fail, count);    // records of failed pods kept per scenario (ksim_sweep_explain)
   // Tree form (ksim_tree.hip): one tree-mode wave per scenario, scenarios spread over the CUs.
   if (!getenv("KSIM_SWEEP_SCAN") && h->n_tcls > 0 && n < ((int64_t)1 << 24) && !h->pfast_off) {
     KsimTreeGeo g{};
@@ -1696,7 +1781,7 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
       const size_t N = (size_t)n, P = (size_t)count, K = (size_t)g.K;
       const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
       const size_t per = al(4 * N * 8) + al(N * 4) + al(K * g.st[0] * 4) + al(g.level_entries * 8) + al(K * 4) + al(8) +
-                         al(P * 4) + al(sizeof(kf64::EvCfg)) + (MW ? al(MW) : 0);
+                         al(P * 4) + al(sizeof(kf64::EvCfg)) + (MW ? al(MW) : 0) + al(why_bytes(wcap));
       // scratch budget: at most 24 GiB (all 4,096 C5 scenarios, ~3.7 MB each, in one launch) and
       // at most half of the device memory free now (a shared or smaller device gets smaller chunks)
       size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
@@ -1705,7 +1790,8 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
       if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
       auto need_of = [&](size_t C) {
         return C * (al(4 * N * 8) + al(N * 4)) + al(C * K * g.st[0] * 4) + al(C * g.level_entries * 8) + al(C * K * 4) +
-               al(C * 8) + al(C * P * 4) + al(C * sizeof(kf64::EvCfg)) + (MW ? al(C * MW) : 0) + 4096;
+               al(C * 8) + al(C * P * 4) + al(C * sizeof(kf64::EvCfg)) + (MW ? al(C * MW) : 0) +
+               (wcap ? al(C * wcap * 4) + al(C * wcap * KSIM_NREASONS * 4) : 0) + 4096;
       };
       if (h->swt_bytes < need_of((size_t)chunk)) {
         if (h->swt_scratch) {
@@ -1746,6 +1832,11 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
       kf64::EvCfg* dcfg = (kf64::EvCfg*)take(C * sizeof(kf64::EvCfg));
       sw.cfg = dcfg;
       uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
+      if (wcap) {  // the chunk's records of failed pods
+        sw.why_cap = wcap;
+        sw.why_pod = (int32_t*)take(C * wcap * 4);
+        sw.why_hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
+      }
       std::vector<kf64::EvCfg> cfgs((size_t)n_scen);
       for (int32_t sidx = 0; sidx < n_scen; ++sidx)
         cfgs[sidx] = kf64::make_evcfg(c.preds, c.no_prio != 0, w3[3 * sidx], w3[3 * sidx + 1], w3[3 * sidx + 2]);
@@ -1782,6 +1873,11 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
         dms += b_ms + r_ms;
         HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, sw.out_node, (size_t)sw.nsc * P * 4, hipMemcpyDeviceToHost));
         if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, sw.counter, (size_t)sw.nsc * 8, hipMemcpyDeviceToHost));
+        if (int rcw = why_copy_out(h, fail, wcap, s0, sw.nsc, count, out_node + (size_t)s0 * P, sw.why_pod, sw.why_hist)) {
+          c.first = save_first;
+          c.end = save_end;
+          return rcw;
+        }
       }
       c.first = save_first;
       c.end = save_end;
@@ -1805,6 +1901,7 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
         st->blocks = chunk;
       }
       sweep_scheduled(out_node, n_scen, count, out_scheduled);
+      why_counts(fail, absent, n, n_scen, count, out_node);
       return KSIM_OK;
     }
   }
@@ -1823,11 +1920,12 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
   const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
   const size_t b_pod = al(P * sizeof(kf64::FPod)), b_w = al(S * 12);
   auto need_of = [&](size_t C) {
-    return 4 * al(C * N * 8) + al(C * N * 4) + b_pod + b_w + al(C * P * 4) + al(C * 8) + (MW ? al(C * MW) : 0);
+    return 4 * al(C * N * 8) + al(C * N * 4) + b_pod + b_w + al(C * P * 4) + al(C * 8) + (MW ? al(C * MW) : 0) +
+           (wcap ? al(C * wcap * 4) + al(C * wcap * KSIM_NREASONS * 4) : 0);
   };
   size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
   if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
-  const size_t per = N * 36 + P * 4 + 8 + MW;
+  const size_t per = N * 36 + P * 4 + 8 + MW + why_bytes(wcap);
   int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
   if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
   if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
@@ -1855,7 +1953,7 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
   const size_t C = (size_t)chunk;
   char* q = (char*)h->sw_scratch;
   auto take = [&](size_t b) { char* r = q; q += al(b); return r; };
-  SwArgs a{};
+  SwArgsWhy a{};
   a.n = n; a.n_pods = (int32_t)count;
   a.dac = h->sw_dac; a.dam = h->sw_dam; a.yc = h->sw_yc; a.ym = h->sw_ym;
   a.allowed = c.allowed_pods; a.flags = c.flags;
@@ -1868,6 +1966,11 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
   a.out_node = (int32_t*)take(C * P * 4);
   a.out_counter = (uint64_t*)take(C * 8);
   uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
+  if (wcap) {  // the chunk's records of failed pods
+    a.why.cap = wcap;
+    a.why.pod = (int32_t*)take(C * wcap * 4);
+    a.why.hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
+  }
   a.preds = c.preds; a.no_prio = c.no_prio;
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 12, hipMemcpyHostToDevice, ksim_stream(h)));
@@ -1886,6 +1989,7 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
     ms += c_ms;
     HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
     if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
+    if (int rcw = why_copy_out(h, fail, wcap, s0, nsc, count, out_node + (size_t)s0 * P, a.why.pod, a.why.hist)) return rcw;
   }
   if (st) {
     memset(st, 0, sizeof *st);
@@ -1901,19 +2005,29 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
     st->blocks = chunk;
   }
   sweep_scheduled(out_node, n_scen, count, out_scheduled);
+  why_counts(fail, absent, n, n_scen, count, out_node);
   return KSIM_OK;
 }
 
 int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count, int32_t* out_node,
                uint64_t* out_counters, ksim_stats* st) {
   if (!weights) return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep: null argument");
-  return sweep_impl(h, "ksim_sweep", weights, nullptr, n_scen, first, count, out_node, out_counters, nullptr, st);
+  return sweep_impl(h, "ksim_sweep", weights, nullptr, n_scen, first, count, out_node, out_counters, nullptr, nullptr, st);
 }
 
 int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
                      int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled, ksim_stats* st) {
   return sweep_impl(h, "ksim_sweep_nodes", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
-                    st);
+                    nullptr, st);
+}
+
+int ksim_sweep_explain(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
+                       int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
+                       const ksim_sweep_failures* fail, ksim_stats* st) {
+  if (fail && (fail->cap < 0 || (fail->cap > 0 && (!fail->pod || !fail->hist))))
+    return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep_explain: a negative record cap, or a cap without record arrays");
+  return sweep_impl(h, "ksim_sweep_explain", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
+                    fail, st);
 }
 
 int ksim_shard_setup(ksim_handle* h, int32_t rank, int32_t world, int64_t node_base) {

@@ -3,6 +3,15 @@
 #pragma once
 #include "ksim_f64.h"
 
+// Explained sweeps (ksim_sweep_explain, the WHY instantiations): scenario s of a chunk keeps the
+// first cap failed pods of its queue, record k = (pod[s][k], hist[s][k][KSIM_NREASONS]).  Only the
+// WHY instantiations take it (SwArgsWhy, SwgArgsWhy): the others keep their kernel arguments.
+struct SwWhy {
+  int32_t cap;
+  int32_t* pod;   // [C][cap] index of the k-th failed pod, relative to the range's first
+  int32_t* hist;  // [C][cap][KSIM_NREASONS] its FitError histogram
+};
+
 struct SwArgs {
   int64_t n;
   int32_t n_pods, scen0;
@@ -24,6 +33,9 @@ struct SwArgs {
   uint64_t counter0;
   int32_t* out_node;      // [S][n_pods]
   uint64_t* out_counter;  // [S]
+};
+struct SwArgsWhy : SwArgs {
+  SwWhy why;  // cap == 0: an unexplained launch, of the WHY = false instantiation on the SwArgs part
 };
 
 #define KSIM_SWEEP_MAX_NODES 76800  // uint16 evaluations of one scenario in LDS (150 KiB)
@@ -50,9 +62,12 @@ struct SwgArgs {
   int32_t* out_node;      // [C][n_pods]
   uint64_t* out_counter;  // [C]
 };
+struct SwgArgsWhy : SwgArgs {
+  SwWhy why;
+};
 
 // one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
 #define KSIM_SWEEP_GENERAL_MAX_NODES 38400
 #define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word
 static_assert(KSIM_MAX_RCLASS <= 16, "the reduce class takes the low four bits of a packed evaluation");
-static_assert(sizeof(KsimCtx) + sizeof(SwgArgs) <= 4096 - 64, "KsimCtx + SwgArgs exceed the kernel-argument limit");
+static_assert(sizeof(KsimCtx) + sizeof(SwgArgsWhy) <= 4096 - 64, "KsimCtx + SwgArgs exceed the kernel-argument limit");

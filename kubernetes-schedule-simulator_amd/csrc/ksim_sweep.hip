@@ -30,6 +30,14 @@
 // exact int64 one of the scheduling kernels (ksim_predicates_a, ksim_map_score, ksim_rclass_a), LDS
 // holds (map score << 4) | reduce class per node, and the pod's end is ksim_decide_lanes over the
 // per-class (max, count at max) of the workgroup.
+//
+// Explained sweeps (ksim_sweep_explain, include/ksim_whatif.h): the WHY instantiations of both
+// kernels keep, per scenario, the first cap failed pods with their FitError histogram.  A pod that
+// fits nowhere is evaluated once more for its reason masks — the packed evaluations in LDS have no
+// room for them — and the masks of the listed nodes are counted per reason.  The WHY = false
+// instantiations are the kernels as they were, kernel arguments included.
+#include <type_traits>
+
 #include "ksim_decide.h"
 #include "ksim_sweep.h"
 #include "ksim_wave.h"
@@ -40,14 +48,39 @@ namespace {
 constexpr int SB = 1024;      // threads per scenario workgroup
 constexpr int SW = SB / 64;   // waves
 constexpr uint16_t NOFIT = 0xFFFF;
+
+// FitError histogram of a failed pod (the WHY instantiations): the wave's reason masks, one row per
+// lane (0 = no row, an absent node, or a node that fits), into the workgroup's LDS histogram — one
+// ballot, popcount and LDS atomic add per reason present in the wave.  Wave-uniform control flow.
+__device__ __forceinline__ void why_add(uint32_t rm, int lane, int32_t* s_hist) {
+  uint64_t b;
+  while ((b = __ballot(rm != 0))) {
+    const uint32_t ml = (uint32_t)__builtin_amdgcn_readlane((int)rm, __builtin_ctzll(b));
+    const int r = __builtin_ctz(ml);
+    const int32_t nr = (int32_t)__popcll(__ballot((rm >> r) & 1u));
+    if (lane == 0) atomicAdd(&s_hist[r], nr);
+    rm &= ~(1u << r);
+  }
+}
+
+// the record of the scenario's k-th failed pod, pod p of the range: threads 0..31 the histogram,
+// thread 0 the pod (after the barrier that ends the histogram pass)
+__device__ __forceinline__ void why_store(const SwWhy& y, int s, int32_t k, int32_t p, int tid, const int32_t* s_hist) {
+  const int64_t rec = (int64_t)s * y.cap + k;
+  if (tid < KSIM_NREASONS) y.hist[rec * KSIM_NREASONS + tid] = s_hist[tid];
+  if (tid == 0) y.pod[rec] = p;
+}
 }  // namespace
 
 
-template <bool ABS>
-__global__ __launch_bounds__(SB) void ksim_sweep_kernel(SwArgs a) {
+// WHY (ksim_sweep_explain): a pod that fits nowhere is evaluated once more for its reason masks
+// while the scenario has kept fewer than cap records; nothing else differs.
+template <bool ABS, bool WHY>
+__global__ __launch_bounds__(SB) void ksim_sweep_kernel(std::conditional_t<WHY, SwArgsWhy, SwArgs> a) {
   extern __shared__ uint16_t sc[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
   __shared__ int32_t s_wtot[SW];
+  int32_t nfail = 0;  // WHY: failed pods of this scenario so far (uniform)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int s = blockIdx.x;
   const int64_t n = a.n;
@@ -96,7 +129,30 @@ __global__ __launch_bounds__(SB) void ksim_sweep_kernel(SwArgs a) {
     const int32_t C = ksimw::sum_i32((in && mw == M && M >= 0) ? s_red[lane][2] : 0);
     if (F == 0) {  // FitError: no node fits
       if (tid == 0) a.out_node[(int64_t)s * a.n_pods + p] = -1;
-      __syncthreads();  // s_red is rewritten by the next pod
+      if constexpr (WHY) {
+        __shared__ int32_t s_hist[KSIM_NREASONS];
+        if (nfail < a.why.cap) {  // (uniform) one more pass over the rows, for the reason masks
+          if (tid < KSIM_NREASONS) s_hist[tid] = 0;
+          __syncthreads();
+          for (int64_t j0 = tid - lane; j0 < n; j0 += SB) {  // j0: the wave's first row of the round
+            const int64_t j = j0 + lane;
+            uint32_t rmask = 0;
+            if (j < n) {
+              FRow r;
+              r.ac = a.dac[j]; r.am = a.dam[j]; r.yc = a.yc[j]; r.ym = a.ym[j];
+              r.rc = rc[j]; r.rm = rm[j]; r.zc = zc[j]; r.zm = zm[j];
+              r.allowed = a.allowed[j]; r.count = cnt[j]; r.fl = a.flags[j];
+              (void)feval(EC, P, r, rmask);
+              if constexpr (ABS) rmask = r.count < 0 ? 0u : rmask;  // not listed: not evaluated
+            }
+            why_add(rmask, lane, s_hist);
+          }
+          __syncthreads();
+          why_store(a.why, s, nfail, p, tid, s_hist);
+        }
+        ++nfail;
+      }
+      __syncthreads();  // s_red (and s_hist) are rewritten by the next pod
       continue;
     }
     const uint32_t ix = (F > 1) ? (uint32_t)ksim_select_ix(counter, (uint32_t)C) : 0u;
@@ -167,8 +223,11 @@ struct SwgAcc {
 };
 }  // namespace
 
-template <bool ABS>
-__global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* __restrict__ ctxs, const SwgArgs a) {
+// WHY (ksim_sweep_explain): as in the scan form, the reason masks from ksim_predicates_a.  The packed
+// word in LDS cannot carry a mask (27 score bits + 4 class bits), so the pass re-evaluates.
+template <bool ABS, bool WHY>
+__global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* __restrict__ ctxs,
+                                                                const std::conditional_t<WHY, SwgArgsWhy, SwgArgs> a) {
   extern __shared__ uint32_t sg[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
   __shared__ int32_t s_wtot[SW];
@@ -184,6 +243,7 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* _
   const int64_t KS = (n + SB - 1) / SB;  // contiguous segment per thread in the count and select phases
   const int64_t seg0 = (int64_t)tid * KS, seg1 = (seg0 + KS < n) ? seg0 + KS : n;
   uint64_t counter = a.counter0;  // genericScheduler.lastNodeIndex of this scenario
+  int32_t nfail = 0;              // WHY: failed pods of this scenario so far (uniform)
   if (tid < 2 * KSIM_MAX_RCLASS) {
     (&s_M[0][0])[tid] = -1;
     (&s_C[0][0])[tid] = 0;
@@ -257,7 +317,40 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* _
     int32_t C = ksimw::sum_i32((in && mw == M && M >= 0) ? s_red[lane][2] : 0);
     if (F == 0) {  // FitError: no node fits
       if (tid == 0) a.out_node[(int64_t)s * a.n_pods + p] = -1;
-      __syncthreads();  // s_red is rewritten by the next pod
+      if constexpr (WHY) {
+        __shared__ int32_t s_hist[KSIM_NREASONS];
+        if (nfail < a.why.cap) {  // (uniform) one more pass over the rows, for the reason masks
+          if (tid < KSIM_NREASONS) s_hist[tid] = 0;
+          __syncthreads();
+          for (int64_t j0 = tid - lane; j0 < n; j0 += SB) {  // j0: the wave's first row of the round
+            const int64_t j = j0 + lane;
+            uint32_t rmask = 0;
+            if (j < n) {
+              const KsimRow r = ksim_load_row(c, j);
+              bool listed = true;
+              if constexpr (ABS) listed = r.count >= 0;  // not listed: not evaluated
+              if (listed) {
+                SwgAcc acc{c, true, true, true, 0, 0};
+                if (P.flags & (KSIM_POD_NEED_SELECTOR | KSIM_POD_NEED_TAINTS)) {
+                  const int64_t cl = P.cls;
+                  if (P.flags & KSIM_POD_NEED_SELECTOR) acc.sel = ksim_bit(c.sel_ok, cl, c.lwords, c.label_set[j]);
+                  if (P.flags & KSIM_POD_NEED_TAINTS) {
+                    const int32_t ts = c.taint_set[j];
+                    acc.tok = ksim_bit(c.taint_ok, cl, c.twords, ts);
+                    acc.nok = ksim_bit(c.noexec_ok, cl, c.twords, ts);
+                  }
+                }
+                rmask = ksim_predicates_a<SwgAcc, true, true>(c, P, j, r, acc);
+              }
+            }
+            why_add(rmask, lane, s_hist);
+          }
+          __syncthreads();
+          why_store(a.why, s, nfail, p, tid, s_hist);
+        }
+        ++nfail;
+      }
+      __syncthreads();  // s_red (and s_hist) are rewritten by the next pod
       continue;
     }
     uint32_t win = 1u;
@@ -402,7 +495,7 @@ extern "C" hipError_t ksim_sweep_prepare(const int64_t* ac, const int64_t* am, i
 }
 
 extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, const int64_t* zc0, const int64_t* zm0,
-                                        const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgs* args,
+                                        const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgsWhy* args,
                                         int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
                                         hipEvent_t ev1, hipStream_t st) {
   const int64_t n = args->n, total = n * (int64_t)n_scen;
@@ -416,10 +509,16 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ev0) (void)hipEventRecord(ev0, st);
-  if (absent)
-    hipLaunchKernelGGL(ksim_sweep_kernel<true>, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
+  const size_t lds = (size_t)n * sizeof(uint16_t);
+  const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
+  if (absent && why)
+    hipLaunchKernelGGL((ksim_sweep_kernel<true, true>), dim3((unsigned)n_scen), dim3(SB), lds, st, *args);
+  else if (absent)
+    hipLaunchKernelGGL((ksim_sweep_kernel<true, false>), dim3((unsigned)n_scen), dim3(SB), lds, st, (const SwArgs&)*args);
+  else if (why)
+    hipLaunchKernelGGL((ksim_sweep_kernel<false, true>), dim3((unsigned)n_scen), dim3(SB), lds, st, *args);
   else
-    hipLaunchKernelGGL(ksim_sweep_kernel<false>, dim3((unsigned)n_scen), dim3(SB), (size_t)n * sizeof(uint16_t), st, *args);
+    hipLaunchKernelGGL((ksim_sweep_kernel<false, false>), dim3((unsigned)n_scen), dim3(SB), lds, st, (const SwArgs&)*args);
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;
@@ -427,7 +526,7 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
 
 // The general form: hc the handle's context, cols the chunk's scenario columns, err the sweep's own
 // error word (ksim_commit's port-slot overflow bit; the handle's word is never written).
-extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgs* args,
+extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsWhy* args,
                                                 int32_t n_scen, const uint32_t* absent, int32_t absent_words,
                                                 int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
@@ -449,12 +548,19 @@ extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols
   hipLaunchKernelGGL(ksim_sweep_general_ctx_kernel, dim3((unsigned)((n_scen + 63) / 64)), dim3(64), 0, st, k, args->w,
                      args->scen0, n_scen, args->ctx);
   const size_t lds = (size_t)n * sizeof(uint32_t);
-  if (absent)
-    hipLaunchKernelGGL(ksim_sweep_general_kernel<true>, dim3((unsigned)n_scen), dim3(SB), lds, st,
+  const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
+  if (absent && why)
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true>), dim3((unsigned)n_scen), dim3(SB), lds, st,
+                       (const KsimCtx*)args->ctx, *args);
+  else if (absent)
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, false>), dim3((unsigned)n_scen), dim3(SB), lds, st,
+                       (const KsimCtx*)args->ctx, (const SwgArgs&)*args);
+  else if (why)
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, true>), dim3((unsigned)n_scen), dim3(SB), lds, st,
                        (const KsimCtx*)args->ctx, *args);
   else
-    hipLaunchKernelGGL(ksim_sweep_general_kernel<false>, dim3((unsigned)n_scen), dim3(SB), lds, st,
-                       (const KsimCtx*)args->ctx, *args);
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, false>), dim3((unsigned)n_scen), dim3(SB), lds, st,
+                       (const KsimCtx*)args->ctx, (const SwgArgs&)*args);
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;

@@ -52,6 +52,11 @@ struct KsimTreeSweep {
   uint64_t* counter;
   int32_t* out_node;
   const void* cfg;
+  // explained sweeps (ksim_sweep_explain): why_cap > 0 keeps each scenario's first why_cap failed
+  // pods, record k = (why_pod[s][k], why_hist[s][k][KSIM_NREASONS])
+  int32_t why_cap;
+  int32_t* why_pod;
+  int32_t* why_hist;
 };
 
 #ifdef __cplusplus

@@ -74,6 +74,10 @@ struct TreeArgs {
   int32_t nsc;
   const kf64::EvCfg* sw_cfg;
   int64_t sw_count;  // output row length (pods of the call)
+  // explained sweep (ksim_sweep_explain; collect != 0 in sweep mode): scenario s keeps its first
+  // why_cap failed pods, record k = (why_pod[s][k], out_reasons[s][k][KSIM_NREASONS])
+  int32_t why_cap;
+  int32_t* why_pod;
 };
 
 // Scenario s's view of the arguments (nsc > 0).
@@ -85,6 +89,10 @@ __device__ __forceinline__ void scen_ptrs(TreeArgs& a, int s) {
   a.fitc += (int64_t)s * a.g.K;
   a.counter += s;
   a.out_node += (int64_t)s * a.sw_count - a.first;
+  if (a.collect) {
+    a.out_reasons += (int64_t)s * a.why_cap * KSIM_NREASONS;
+    a.why_pod += (int64_t)s * a.why_cap;
+  }
   a.cfg = a.sw_cfg[s];
 }
 
@@ -394,7 +402,11 @@ __global__ __launch_bounds__(128) void ksim_tree_kernel(TreeArgs a0) {
   // lane k: the last pod of class k whose FitError histogram (in out_reasons) still holds — a
   // failing pod commits nothing, so until the next commit every class's histogram stays valid
   // (past saturation, where nearly every pod fails, each class is scanned once per commit)
+  // In an explained sweep the record index (the scenario's failed pods so far, nfail) takes the
+  // pod index's place, as the store address and as what hist_pod remembers; past why_cap nothing is
+  // kept, so a remembered index is always a kept record.
   int64_t hist_pod = -1;
+  int64_t nfail = 0;
   int64_t p = a.first;
   int64_t ready = a.first;  // pods below this are in the ring
   bool stop = false;
@@ -417,27 +429,34 @@ __global__ __launch_bounds__(128) void ksim_tree_kernel(TreeArgs a0) {
     const uint32_t F = (uint32_t)__builtin_amdgcn_readlane(fitv, k);
     if (F == 0) {  // FitError: no commit, lastNodeIndex unchanged
       if (lane == 0) a.out_node[p] = -1;
-      if (a.collect) {
+      const int64_t ri = a.nsc ? nfail : p;  // where this pod's histogram goes
+      if (a.collect && a.nsc) ++nfail;
+      if (a.collect && (!a.nsc || ri < a.why_cap)) {
         const int64_t pk = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)((uint64_t)hist_pod >> 32), k) << 32) |
                                      (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)hist_pod, k));
         if (pk >= 0) {  // same wave wrote it: program order makes the load see the store
-          if (lane < KSIM_NREASONS) a.out_reasons[p * KSIM_NREASONS + lane] = a.out_reasons[pk * KSIM_NREASONS + lane];
+          if (lane < KSIM_NREASONS) a.out_reasons[ri * KSIM_NREASONS + lane] = a.out_reasons[pk * KSIM_NREASONS + lane];
         } else {  // histogram of first-failing-predicate reasons over every node
           if (lane < KSIM_NREASONS) s_hist[lane] = 0;
           const kf64::FPod P = class_pod(s_cls[k]);
           for (int i0 = 0; i0 < n; i0 += 64) {
             const int i = i0 + lane;
             uint32_t rm = 0;
-            if (i < n) (void)kf64::feval(a.cfg, P, load_row(a, i), rm);
+            if (i < n) {
+              const kf64::FRow row = load_row(a, i);
+              (void)kf64::feval(a.cfg, P, row, rm);
+              rm = row.count < 0 ? 0u : rm;  // a node the scenario does not list is not evaluated
+            }
             if (__ballot(rm != 0))
               for (int r = 0; r < KSIM_NREASONS; ++r) {
                 const int nr = __popcll(__ballot((rm >> r) & 1u));
                 if (lane == 0 && nr) s_hist[r] += nr;
               }
           }
-          hist_pod = lane == k ? p : hist_pod;
-          if (lane < KSIM_NREASONS) a.out_reasons[p * KSIM_NREASONS + lane] = s_hist[lane];
+          hist_pod = lane == k ? ri : hist_pod;
+          if (lane < KSIM_NREASONS) a.out_reasons[ri * KSIM_NREASONS + lane] = s_hist[lane];
         }
+        if (a.nsc && lane == 0) a.why_pod[ri] = (int32_t)(p - a.first);
       }
       ++p;
       if (lane == 0) __hip_atomic_store(&s_done, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -655,7 +674,10 @@ TreeArgs make_args(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* 
     a.out_node = sw->out_node;
     a.sw_cfg = (const kf64::EvCfg*)sw->cfg;
     a.sw_count = sw->count_pods;
-    a.collect = 0;
+    a.collect = sw->why_cap > 0;
+    a.why_cap = sw->why_cap;
+    a.why_pod = sw->why_pod;
+    a.out_reasons = sw->why_hist;
   }
   return a;
 }

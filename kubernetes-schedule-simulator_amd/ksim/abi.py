@@ -130,6 +130,11 @@ class NodeRow(C.Structure):
                 ("alloc_scalar", _i64p), ("req_scalar", _i64p), ("ports", _u64p)]
 
 
+class SweepFailures(C.Structure):
+    """ksim_sweep_failures (include/ksim_whatif.h): the caller's arrays for the failed pods' records."""
+    _fields_ = [("cap", C.c_int32), ("count", _i32p), ("listed", _i32p), ("pod", _i32p), ("hist", _i32p)]
+
+
 SCHEDULE_ONLY, SCHEDULE_ASSUME = 0, 1
 
 
@@ -245,6 +250,9 @@ def lib():
                              C.POINTER(Stats)]
     L.ksim_sweep_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    # include/ksim_whatif.h (not part of ksim.h's function list, so not in EXPORTS)
+    L.ksim_sweep_explain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(Stats)]
     podargs = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     L.ksim_schedule_one.argtypes = [C.c_void_p] + podargs + [C.c_int32, C.POINTER(Result)]
     L.ksim_pod_add.argtypes = [C.c_void_p, C.c_int64] + podargs

@@ -457,7 +457,7 @@ class GenericScheduler:
         self.last_stats = st
         return out, reasons, st
 
-    def sweep(self, scenarios, first=0, count=None, absent=None):
+    def sweep(self, scenarios, first=0, count=None, absent=None, explain=None):
         """Capacity-planning what-if (ksim_sweep): every scenario — a prioritizer list of map
         priorities, e.g. [("LeastRequestedPriority", 3), ("BalancedResourceAllocation", 1)] —
         schedules pods [first, first+count) on its own copy of the current node state, from the
@@ -481,9 +481,24 @@ class GenericScheduler:
         CheckServiceAffinity with services selecting the pods, more than abi.MAX_RCLASS reduce
         classes in a pod class, a node-sharded scheduler, a scenario with a reduce priority, and
         explicit scenarios over such a queue when this scheduler's own policy has a reduce
-        priority or a NodePreferAvoidPods addend (pass scenarios=None with absent sets)."""
+        priority or a NodePreferAvoidPods addend (pass scenarios=None with absent sets).
+
+        explain (ksim_sweep_explain, include/ksim_whatif.h): True keeps the FitError histogram of
+        every failed pod of every scenario, an int at most that many per scenario (the first in
+        queue order); None or False is the unexplained call.  Placements, counters and stats are
+        those of the same sweep without explain, and the return value stays (placements,
+        counters, stats).  self.last_failures is then dict(count [n_scen] failed pods (may exceed
+        the cap), listed [n_scen] nodes the scenario lists — the N of "0/N nodes are available" —,
+        pod [n_scen][cap] index relative to first of the k-th failed pod, hist [n_scen][cap]
+        [abi.NREASONS] its histogram over the listed nodes), pod and hist -1 past the
+        min(count, cap) kept records; fit_error_message(listed, hist, scalar_names) is the
+        reference's text.  A scenario that lists no node fails every pod with an all-zero
+        histogram and listed 0 (the reference's ErrNoNodesAvailable).  Works with and without
+        absent, with and without scenario weights, in every form."""
         n = len(self._pods)
         count = n - first if count is None else count
+        if explain is not None and explain is not False:
+            return self._sweep_explain(scenarios, first, count, absent, count if explain is True else int(explain))
         if absent is not None:
             return self._sweep_nodes(scenarios, first, count, absent)
         w = np.zeros((len(scenarios), abi.NW), np.int64)
@@ -499,6 +514,39 @@ class GenericScheduler:
         self.last_stats = st
         return out, ctr, st
 
+    def _sweep_weights(self, scenarios):
+        w = np.zeros((len(scenarios), abi.NW), np.int64)
+        for k, pri in enumerate(scenarios):
+            cfg = make_config(self.predicates, pri)
+            if cfg.no_priorities != self.cfg.no_priorities:
+                raise Unsupported("a sweep scenario needs a non-empty prioritizer list like the scheduler's")
+            w[k] = list(cfg.weights)
+        return w
+
+    def _sweep_explain(self, scenarios, first, count, absent, cap):
+        mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
+        if mask is None and scenarios is None:
+            raise abi.KsimError(abi.E_INVAL, "sweep: neither scenarios nor absent sets")
+        S = len(scenarios) if mask is None else len(mask)
+        if scenarios is not None and len(scenarios) != S:
+            raise abi.KsimError(abi.E_INVAL, "sweep: %d scenarios but %d absent sets" % (len(scenarios), S))
+        w = None if scenarios is None else self._sweep_weights(scenarios)
+        out = np.zeros((S, count), np.int32)
+        ctr = np.zeros(S, np.uint64)
+        bound = np.zeros(S, np.int32)
+        fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
+                     pod=np.full((S, max(cap, 0)), -1, np.int32),
+                     hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
+        f = abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
+                              abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32))
+        st = abi.Stats()
+        self.h.call("ksim_sweep_explain", abi.vptr(w), abi.vptr(mask), S, first, count, abi.vptr(out), abi.vptr(ctr),
+                    abi.vptr(bound), C.byref(f), C.byref(st))
+        self.last_stats = st
+        self.last_scheduled = bound
+        self.last_failures = fails
+        return out, ctr, st
+
     def _sweep_nodes(self, scenarios, first, count, absent):
         mask = absent_mask(self.cluster.n_nodes, absent)
         S = len(mask)
@@ -506,12 +554,7 @@ class GenericScheduler:
         if scenarios is not None:
             if len(scenarios) != S:
                 raise abi.KsimError(abi.E_INVAL, "sweep: %d scenarios but %d absent sets" % (len(scenarios), S))
-            w = np.zeros((S, abi.NW), np.int64)
-            for k, pri in enumerate(scenarios):
-                cfg = make_config(self.predicates, pri)
-                if cfg.no_priorities != self.cfg.no_priorities:
-                    raise Unsupported("a sweep scenario needs a non-empty prioritizer list like the scheduler's")
-                w[k] = list(cfg.weights)
+            w = self._sweep_weights(scenarios)
         out = np.zeros((S, count), np.int32)
         ctr = np.zeros(S, np.uint64)
         bound = np.zeros(S, np.int32)
@@ -838,7 +881,7 @@ class ClusterCapacity:
         rep.review = get_report(rep.status)
         return rep
 
-    def what_if(self, outages, first=0, count=None):
+    def what_if(self, outages, first=0, count=None, explain=False):
         """Node-outage what-ifs over the snapshot (ksim_sweep_nodes): for every outage — (name, node
         names or indices), or the output of outage_sets — the whole queue is scheduled on the
         snapshot without those nodes, under the simulator's own provider or policy, all outages in
@@ -849,7 +892,12 @@ class ClusterCapacity:
         provider or policy; queues with inter-pod affinity, spread or volume state are refused
         (KsimUnsupported), as by GenericScheduler.sweep.
         Returns one record per outage: dict(name, absent (node count), scheduled, failed,
-        placements [(pod name, node name or None)] in queue order)."""
+        placements [(pod name, node name or None)] in queue order).
+        explain (ksim_sweep_explain): True, or an int cap per outage — each record gains listed (the
+        nodes the outage leaves), fit_errors [(pod name, message)] of its failed pods in queue order,
+        the message the reference's FitError text over the listed nodes ("0/N nodes are available:
+        ...") or report.ERR_NO_NODES when the outage leaves no node, and explained, how many of the
+        failed pods fit_errors holds (all of them, or the cap)."""
         cl = self.cluster
         outages = list(outages)
         sets_ = []
@@ -867,14 +915,24 @@ class ClusterCapacity:
         predicates, priorities, kw = self._sched_args
         g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
         try:
-            out, _, _ = g.sweep(None, first, count, absent=sets_)
+            out, _, _ = g.sweep(None, first, count, absent=sets_, explain=explain if explain else None)
+            fails = g.last_failures if explain else None
         finally:
             g.close()
         names = cl.names
         pod_names = cl.pod_names[first:first + out.shape[1]]
         recs = []
-        for (name, _), idx, row in zip(outages, sets_, out):
+        for s, ((name, _), idx, row) in enumerate(zip(outages, sets_, out)):
             bound = int((row >= 0).sum())
             recs.append(dict(name=name, absent=len(idx), scheduled=bound, failed=len(row) - bound,
                              placements=[(pn, names[w] if w >= 0 else None) for pn, w in zip(pod_names, row)]))
+            if fails is not None:
+                from .report import ERR_NO_NODES
+                listed = int(fails["listed"][s])
+                kept = min(int(fails["count"][s]), fails["pod"].shape[1])
+                scal = cl.scalar_names.items
+                recs[-1].update(listed=listed, explained=kept, fit_errors=[
+                    (pod_names[int(fails["pod"][s, k])],
+                     fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
+                    for k in range(kept)])
         return recs
