@@ -1,5 +1,5 @@
-// ksim_runtime.cpp — host side of libksim.so: the C-ABI declared in include/ksim.h and
-// include/ksim_whatif.h.
+// ksim_runtime.cpp — host side of libksim.so: the C-ABI declared in include/ksim.h,
+// include/ksim_whatif.h and include/ksim_drain.h.
 //
 // Owns the device-resident node table (SoA columns in HBM), the pod-class tables, the
 // pod queue and the run state, and drives the scan kernels on one HIP stream per handle.
@@ -7,6 +7,7 @@
 // land on any OS thread) and returns a KSIM_* status.
 #include "ksim_handle.h"
 
+#include "../../include/ksim_drain.h"
 #include "../../include/ksim_whatif.h"
 
 namespace {
@@ -1486,6 +1487,12 @@ static void sweep_scheduled(const int32_t* out_node, int32_t n_scen, int64_t cou
 }
 
 // ---- ksim_sweep_explain (include/ksim_whatif.h): the failed pods' records ----
+// failed pods of scenario s's prefix queue (ksim_sweep_drain; none without one)
+static int64_t pre_failed(const ksim_sweep_requeue* rq, int32_t s) {
+  int64_t nf = 0;
+  for (int64_t k = rq ? rq->off[s] : 0; rq && k < rq->off[s + 1]; ++k) nf += rq->out_node[k] < 0;
+  return nf;
+}
 // Records a scenario keeps on the device: none without a record array, and never more than the
 // range has pods.
 static int32_t why_cap(const ksim_sweep_failures* fail, int64_t count) {
@@ -1497,13 +1504,15 @@ static size_t why_bytes(int32_t cap) { return (size_t)cap * (1 + KSIM_NREASONS) 
 // A chunk's records ([nsc][cap] pods, [nsc][cap][KSIM_NREASONS] histograms on the device) into the
 // caller's arrays at the chunk's scenario offset s0: per scenario the first min(failed, cap), the
 // words past them left unwritten.  out_node: the chunk's placements, already on the host.
+// rq (ksim_sweep_drain): the scenarios' prefix answers, already on the host, count as well.
 static int why_copy_out(ksim_handle* h, const ksim_sweep_failures* fail, int32_t cap, int32_t s0, int32_t nsc,
-                        int64_t count, const int32_t* out_node, const int32_t* dpod, const int32_t* dhist) {
+                        int64_t count, const int32_t* out_node, const int32_t* dpod, const int32_t* dhist,
+                        const ksim_sweep_requeue* rq = nullptr) {
   if (!cap) return KSIM_OK;
   std::vector<int32_t> kept((size_t)nsc);
   size_t total = 0;
   for (int32_t s = 0; s < nsc; ++s) {
-    int64_t nf = 0;
+    int64_t nf = pre_failed(rq, s0 + s);
     for (int64_t k = 0; k < count; ++k) nf += out_node[(size_t)s * count + k] < 0;
     kept[s] = (int32_t)std::min<int64_t>(nf, cap);
     total += (size_t)kept[s];
@@ -1537,12 +1546,12 @@ static int why_copy_out(ksim_handle* h, const ksim_sweep_failures* fail, int32_t
 
 // count[s] = failed pods, listed[s] = n - |absent set of s| (bits at or above n ignored)
 static void why_counts(const ksim_sweep_failures* fail, const uint32_t* absent, int64_t n, int32_t n_scen, int64_t count,
-                       const int32_t* out_node) {
+                       const int32_t* out_node, const ksim_sweep_requeue* rq = nullptr) {
   if (!fail) return;
   const int32_t aw = (int32_t)((n + 31) / 32);
   for (int32_t s = 0; s < n_scen; ++s) {
     if (fail->count) {
-      int32_t nf = 0;
+      int32_t nf = (int32_t)pre_failed(rq, s);
       for (int64_t k = 0; k < count; ++k) nf += out_node[(size_t)s * count + k] < 0;
       fail->count[s] = nf;
     }
@@ -1560,12 +1569,18 @@ static void why_counts(const ksim_sweep_failures* fail, const uint32_t* absent, 
 
 // The general form of the sweep (ksim_sweep_general_kernel): a range with a pod that is not
 // resource-only.  Arguments as sweep_impl, which has checked them.
+// rq (ksim_sweep_drain, which has checked it): every scenario's prefix queue, scheduled before the
+// range; count may then be 0 and weights are NULL.
 static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
                          int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                         const ksim_sweep_failures* fail, ksim_stats* st) {
+                         const ksim_sweep_failures* fail, ksim_stats* st, const ksim_sweep_requeue* rq = nullptr,
+                         int32_t* out_rehosted = nullptr) {
   KsimCtx& c = h->ctx;
   const int64_t n = c.n;
-  const int32_t wcap = why_cap(fail, count);
+  const size_t T = rq ? (size_t)rq->off[n_scen] : 0;  // prefix pods of all scenarios
+  int64_t mmax = 0;
+  for (int32_t s = 0; rq && s < n_scen; ++s) mmax = std::max(mmax, rq->off[s + 1] - rq->off[s]);
+  const int32_t wcap = why_cap(fail, mmax + count);  // over the longest scenario queue
   if (h->shard.world > 1) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a node-sharded handle sweeps resource-only pods only", who);
   if (n > KSIM_SWEEP_GENERAL_MAX_NODES)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout of pods that are not "
@@ -1580,6 +1595,20 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   if (ksim_rt_range_wide(h, first, count))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod class in the range has more than %d reduce classes", who,
                 KSIM_MAX_RCLASS);
+  if (T) {  // the same refusals for the distinct prefix pods
+    std::vector<int64_t> idx(rq->pod, rq->pod + T);
+    std::sort(idx.begin(), idx.end());
+    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+    for (int64_t q : idx) {
+      if (ksim_rt_aff_count(h, q, 1))
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld carries inter-pod affinity or spread state", who,
+                    (long long)q);
+      if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld mounts volumes", who, (long long)q);
+      if (ksim_rt_range_wide(h, q, 1))
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the class of re-queued pod %lld has more than %d reduce classes", who,
+                    (long long)q, KSIM_MAX_RCLASS);
+    }
+  }
   if (weights && (c.w[KSIM_W_TAINT_TOLERATION] || c.w[KSIM_W_NODE_AFFINITY] || c.use_na))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over pods that are not resource-only would drop the "
                                        "handle's reduce priorities or NodePreferAvoidPods addend (weights = NULL sweeps "
@@ -1615,13 +1644,17 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
   const size_t b_w = weights ? al(S * 24) : 0;
+  // the prefix queues of the whole sweep (off, pod, out_pre): uploaded once, indexed by global scenario
+  const size_t b_rq = rq ? al((S + 1) * 8) + al(T * 8) + al(T * 4) : 0;
   auto need_of = [&](size_t C) {
     return 6 * al(C * N * 8) + 3 * al(C * N * 4) + al(C * N * NS * 8) + al(C * N * NP * 8) + al(C * sizeof(KsimCtx)) + b_w +
-           al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0) + (wcap ? al(C * wcap * 4) + al(C * why_bytes(wcap) - C * wcap * 4) : 0);
+           al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0) + (wcap ? al(C * wcap * 4) + al(C * why_bytes(wcap) - C * wcap * 4) : 0) +
+           b_rq;
   };
   size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
   if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
   const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW + why_bytes(wcap);
+  budget = budget > b_rq ? budget - b_rq : 0;
   int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
   if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
   if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
@@ -1657,7 +1690,7 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   cols.flags = (uint32_t*)take(C * N * 4);
   cols.req_scalar = (int64_t*)take(C * N * NS * 8);
   cols.ports = (uint64_t*)take(C * N * NP * 8);
-  SwgArgsWhy a{};
+  SwgArgsPre a{};
   a.n_pods = (int32_t)count;
   a.first = first;
   a.ctx = (KsimCtx*)take(C * sizeof(KsimCtx));
@@ -1672,6 +1705,15 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     a.why.pod = (int32_t*)take(C * wcap * 4);
     a.why.hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
   }
+  if (rq) {
+    int64_t* doff = (int64_t*)take((S + 1) * 8);
+    int64_t* dpod = (int64_t*)take(T * 8);
+    a.off = doff;
+    a.pod = dpod;
+    a.out_pre = (int32_t*)take(T * 4);
+    HIPCHK(h, hipMemcpyAsync(doff, rq->off, (S + 1) * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+    if (T) HIPCHK(h, hipMemcpyAsync(dpod, rq->pod, T * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+  }
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
@@ -1681,15 +1723,21 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     a.scen0 = s0;  // the chunk's first scenario: its row of the weights
     if (absent)
       HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
-    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h));
+    hipError_t e = rq ? ksim_sweep_drain_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h))
+                      : ksim_sweep_general_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h));
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
     HIPCHK(h, hipEventSynchronize(h->ev1));
     float c_ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
     ms += c_ms;
-    HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
+    if (P) HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
     if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
-    if (int rcw = why_copy_out(h, fail, wcap, s0, nsc, count, out_node + (size_t)s0 * P, a.why.pod, a.why.hist)) return rcw;
+    if (rq && rq->off[s0 + nsc] > rq->off[s0])  // the chunk's prefix answers
+      HIPCHK(h, hipMemcpy(rq->out_node + rq->off[s0], a.out_pre + rq->off[s0],
+                          (size_t)(rq->off[s0 + nsc] - rq->off[s0]) * 4, hipMemcpyDeviceToHost));
+    if (int rcw = why_copy_out(h, fail, wcap, s0, nsc, count, P ? out_node + (size_t)s0 * P : nullptr, a.why.pod,
+                               a.why.hist, rq))
+      return rcw;
   }
   int32_t err = 0;
   HIPCHK(h, hipMemcpy(&err, derr, 4, hipMemcpyDeviceToHost));
@@ -1698,11 +1746,12 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
                                     "more port slots)", who);
   if (st) {
     memset(st, 0, sizeof *st);
-    st->pods = (int64_t)(S * P);
+    st->pods = (int64_t)(S * P + T);
     int64_t b = 0;
     for (size_t k = 0; k < S * P; ++k) b += out_node[k] >= 0;
+    for (size_t k = 0; k < T; ++k) b += rq->out_node[k] >= 0;
     st->scheduled = b;
-    st->node_evals = (int64_t)(S * P) * n;
+    st->node_evals = (int64_t)(S * P + T) * n;
     st->device_ms = ms;
     st->kernel_ms = ms;
     st->kernel_launches = (n_scen + chunk - 1) / chunk;
@@ -1710,7 +1759,9 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     st->blocks = chunk;
   }
   sweep_scheduled(out_node, n_scen, count, out_scheduled);
-  why_counts(fail, absent, n, n_scen, count, out_node);
+  for (int32_t s = 0; out_rehosted && s < n_scen; ++s)
+    out_rehosted[s] = (int32_t)(rq->off[s + 1] - rq->off[s] - pre_failed(rq, s));
+  why_counts(fail, absent, n, n_scen, count, out_node, rq);
   return KSIM_OK;
 }
 
@@ -2019,6 +2070,40 @@ int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* abs
                      int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled, ksim_stats* st) {
   return sweep_impl(h, "ksim_sweep_nodes", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
                     nullptr, st);
+}
+
+int ksim_sweep_drain(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_requeue* rq, int64_t first,
+                     int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
+                     int32_t* out_rehosted, const ksim_sweep_failures* fail, ksim_stats* st) {
+  const char* who = "ksim_sweep_drain";
+  // what needs no device, before the handle is touched
+  if (fail && (fail->cap < 0 || (fail->cap > 0 && (!fail->pod || !fail->hist))))
+    return ksim_fail(h, KSIM_E_INVAL, "%s: a negative record cap, or a cap without record arrays", who);
+  if (n_scen <= 0 || first < 0 || count < 0) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
+  if (!rq || !rq->off) return ksim_fail(h, KSIM_E_INVAL, "%s: null re-queue lists", who);
+  if (rq->off[0] != 0) return ksim_fail(h, KSIM_E_INVAL, "%s: off[0] must be 0", who);
+  for (int32_t s = 0; s < n_scen; ++s) {
+    if (rq->off[s + 1] < rq->off[s]) return ksim_fail(h, KSIM_E_INVAL, "%s: off decreases at scenario %d", who, s);
+    if (rq->off[s + 1] - rq->off[s] > (int64_t)INT32_MAX - count)
+      return ksim_fail(h, KSIM_E_INVAL, "%s: the queue of scenario %d exceeds INT32_MAX pods", who, s);
+  }
+  const int64_t T = rq->off[n_scen];
+  if (T > 0 && (!rq->pod || !rq->out_node))
+    return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pods without a pod or out_node array", who);
+  if (T == 0 && count == 0) return ksim_fail(h, KSIM_E_INVAL, "%s: neither re-queued pods nor a pod range", who);
+  if (count > 0 && !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
+  if (!h) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
+  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
+  if (first + count > h->n_pods) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
+  for (int64_t k = 0; k < T; ++k)
+    if (rq->pod[k] < 0 || rq->pod[k] >= h->n_pods)
+      return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pod index %lld outside the loaded queue of %lld pods", who,
+                  (long long)rq->pod[k], (long long)h->n_pods);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
+  if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
+  return sweep_general(h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
+                       out_rehosted);
 }
 
 int ksim_sweep_explain(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,

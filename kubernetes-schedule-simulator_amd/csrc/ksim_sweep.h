@@ -65,9 +65,19 @@ struct SwgArgs {
 struct SwgArgsWhy : SwgArgs {
   SwWhy why;
 };
+// Drain sweeps (ksim_sweep_drain, include/ksim_drain.h, the PRE instantiations): scenario s (of the
+// whole sweep: scen0 + the workgroup) schedules pods pod[off[s] .. off[s + 1]) of KsimCtx::pods before
+// the range, the answers parallel to pod in out_pre.  A record of why then holds the pod's position
+// in the scenario's own queue (prefix first), and cap counts over that queue.
+struct SwgArgsPre : SwgArgsWhy {
+  const int64_t* off;  // [S + 1]
+  const int64_t* pod;  // [off[S]]
+  int32_t* out_pre;    // [off[S]]
+};
 
 // one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
 #define KSIM_SWEEP_GENERAL_MAX_NODES 38400
 #define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word
 static_assert(KSIM_MAX_RCLASS <= 16, "the reduce class takes the low four bits of a packed evaluation");
 static_assert(sizeof(KsimCtx) + sizeof(SwgArgsWhy) <= 4096 - 64, "KsimCtx + SwgArgs exceed the kernel-argument limit");
+static_assert(sizeof(KsimCtx) + sizeof(SwgArgsPre) <= 4096 - 64, "KsimCtx + SwgArgsPre exceed the kernel-argument limit");

@@ -225,9 +225,18 @@ struct SwgAcc {
 
 // WHY (ksim_sweep_explain): as in the scan form, the reason masks from ksim_predicates_a.  The packed
 // word in LDS cannot carry a mask (27 score bits + 4 class bits), so the pass re-evaluates.
-template <bool ABS, bool WHY>
-__global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* __restrict__ ctxs,
-                                                                const std::conditional_t<WHY, SwgArgsWhy, SwgArgs> a) {
+//
+// PRE (ksim_sweep_drain): the scenario's queue is its prefix pods, then the range.  Step q of it takes
+// pod pre[off + q] for q < m and pod first + q - m after, and answers into out_pre or out_node; m
+// and the pod's index are uniform (scalar loads from the kernel arguments' pointers).  The index of
+// step q + 1 is fetched at the top of step q, so that a step starts with the pod record's load as
+// the range's steps do, not with index -> record -> class tables in a row.  The class words'
+// buffer is the parity of q: the range's own index would repeat the last prefix step's buffer at an
+// odd m.  A record of why holds q.
+template <bool ABS, bool WHY, bool PRE = false>
+__global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
+    const KsimCtx* __restrict__ ctxs,
+    const std::conditional_t<PRE, SwgArgsPre, std::conditional_t<WHY, SwgArgsWhy, SwgArgs>> a) {
   extern __shared__ uint32_t sg[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
   __shared__ int32_t s_wtot[SW];
@@ -249,9 +258,37 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* _
     (&s_C[0][0])[tid] = 0;
   }
   __syncthreads();
+  // PRE: the scenario's prefix pre[0 .. m) and the queue index of its step q (uniform)
+  int32_t m = 0;
+  const int64_t* pre = nullptr;
+  int32_t* out_pre = nullptr;
+  if constexpr (PRE) {
+    const int64_t o0 = a.off[a.scen0 + s];
+    m = (int32_t)(a.off[a.scen0 + s + 1] - o0);
+    pre = a.pod + o0;
+    out_pre = a.out_pre + o0;
+  }
+  const int32_t nq = m + a.n_pods;  // <= INT32_MAX (host-checked)
+  // pre is written before the launch and never by a kernel: read through the constant address space,
+  // a uniform index is then a scalar load whatever the loop has stored since
+  typedef const int64_t __attribute__((address_space(4))) * ConstI64;
+  auto index_of = [&](int32_t q) -> int64_t { return q < m ? ((ConstI64)(uintptr_t)pre)[q] : a.first + (q - m); };
+  auto answer_of = [&](int32_t q) -> int32_t* {
+    if constexpr (PRE) {
+      if (q < m) return out_pre + q;
+    }
+    return a.out_node + ((int64_t)s * a.n_pods + (q - m));
+  };
+  int64_t inext = 0;
+  if constexpr (PRE) inext = nq > 0 ? index_of(0) : 0;
 
-  for (int32_t p = 0; p < a.n_pods; ++p) {
-    const ksim_pod P = c.pods[a.first + p];
+  for (int32_t p = 0; p < nq; ++p) {  // p: the step q of the scenario's queue
+    int64_t ip = a.first + p;
+    if constexpr (PRE) {
+      ip = inext;
+      if (p + 1 < nq) inext = index_of(p + 1);  // in flight during this pod's rows
+    }
+    const ksim_pod P = c.pods[ip];
     const int k1 = (c.w[KSIM_W_TAINT_TOLERATION] != 0) ? c.n_tt[P.cls] : 1;
     const int k2 = c.use_na ? c.n_na[P.cls] : 1;
     const int K = k1 * k2;  // <= KSIM_MAX_RCLASS (host-checked)
@@ -316,7 +353,7 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* _
     const int32_t M = ksimw::max_i32(mw);
     int32_t C = ksimw::sum_i32((in && mw == M && M >= 0) ? s_red[lane][2] : 0);
     if (F == 0) {  // FitError: no node fits
-      if (tid == 0) a.out_node[(int64_t)s * a.n_pods + p] = -1;
+      if (tid == 0) *answer_of(p) = -1;
       if constexpr (WHY) {
         __shared__ int32_t s_hist[KSIM_NREASONS];
         if (nfail < a.why.cap) {  // (uniform) one more pass over the rows, for the reason masks
@@ -406,7 +443,7 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(const KsimCtx* _
         }
       }
       if (jsel >= 0) ksim_commit(c, P, jsel);
-      a.out_node[(int64_t)s * a.n_pods + p] = (int32_t)jsel;
+      *answer_of(p) = (int32_t)jsel;
     }
     __syncthreads();  // the commit (workgroup release/acquire) before the next pod's loads
   }
@@ -526,9 +563,10 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
 
 // The general form: hc the handle's context, cols the chunk's scenario columns, err the sweep's own
 // error word (ksim_commit's port-slot overflow bit; the handle's word is never written).
-extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsWhy* args,
-                                                int32_t n_scen, const uint32_t* absent, int32_t absent_words,
-                                                int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
+// args->off set: the PRE instantiations (ksim_sweep_drain).
+static hipError_t swg_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args, int32_t n_scen,
+                             const uint32_t* absent, int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
+                             hipStream_t st) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
   SwgCols src{hc->req_cpu, hc->req_mem, hc->req_gpu, hc->req_eph, hc->nz_cpu, hc->nz_mem,
               hc->req_scalar, hc->ports, hc->pod_count, hc->port_count, hc->flags};
@@ -549,19 +587,42 @@ extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols
                      args->scen0, n_scen, args->ctx);
   const size_t lds = (size_t)n * sizeof(uint32_t);
   const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
-  if (absent && why)
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true>), dim3((unsigned)n_scen), dim3(SB), lds, st,
-                       (const KsimCtx*)args->ctx, *args);
+  const KsimCtx* ctx = args->ctx;
+  const dim3 grid((unsigned)n_scen), block(SB);
+  if (args->off) {  // ksim_sweep_drain
+    if (absent && why)
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, true>), grid, block, lds, st, ctx, *args);
+    else if (absent)
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, false, true>), grid, block, lds, st, ctx, *args);
+    else if (why)
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<false, true, true>), grid, block, lds, st, ctx, *args);
+    else
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<false, false, true>), grid, block, lds, st, ctx, *args);
+  } else if (absent && why)
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true>), grid, block, lds, st, ctx, (const SwgArgsWhy&)*args);
   else if (absent)
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, false>), dim3((unsigned)n_scen), dim3(SB), lds, st,
-                       (const KsimCtx*)args->ctx, (const SwgArgs&)*args);
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, false>), grid, block, lds, st, ctx, (const SwgArgs&)*args);
   else if (why)
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, true>), dim3((unsigned)n_scen), dim3(SB), lds, st,
-                       (const KsimCtx*)args->ctx, *args);
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, true>), grid, block, lds, st, ctx, (const SwgArgsWhy&)*args);
   else
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, false>), dim3((unsigned)n_scen), dim3(SB), lds, st,
-                       (const KsimCtx*)args->ctx, (const SwgArgs&)*args);
+    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, false>), grid, block, lds, st, ctx, (const SwgArgs&)*args);
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;
+}
+
+extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsWhy* args,
+                                                int32_t n_scen, const uint32_t* absent, int32_t absent_words,
+                                                int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
+  SwgArgsPre a{};
+  (SwgArgsWhy&)a = *args;
+  return swg_launch(hc, cols, &a, n_scen, absent, absent_words, err, ev0, ev1, st);
+}
+
+// The general form with a prefix queue per scenario (ksim_sweep_drain): args->off / pod / out_pre are
+// the whole sweep's, indexed by args->scen0 + the chunk's scenario.
+extern "C" hipError_t ksim_sweep_drain_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
+                                              int32_t n_scen, const uint32_t* absent, int32_t absent_words,
+                                              int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
+  return swg_launch(hc, cols, args, n_scen, absent, absent_words, err, ev0, ev1, st);
 }

@@ -135,6 +135,11 @@ class SweepFailures(C.Structure):
     _fields_ = [("cap", C.c_int32), ("count", _i32p), ("listed", _i32p), ("pod", _i32p), ("hist", _i32p)]
 
 
+class SweepRequeue(C.Structure):
+    """ksim_sweep_requeue (include/ksim_drain.h): the scenarios' prefix queues and their answers."""
+    _fields_ = [("off", _i64p), ("pod", _i64p), ("out_node", _i32p)]
+
+
 SCHEDULE_ONLY, SCHEDULE_ASSUME = 0, 1
 
 
@@ -253,6 +258,10 @@ def lib():
     # include/ksim_whatif.h (not part of ksim.h's function list, so not in EXPORTS)
     L.ksim_sweep_explain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(Stats)]
+    # include/ksim_drain.h (likewise)
+    L.ksim_sweep_drain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepRequeue), C.c_int64, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SweepFailures),
+                                   C.POINTER(Stats)]
     podargs = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     L.ksim_schedule_one.argtypes = [C.c_void_p] + podargs + [C.c_int32, C.POINTER(Result)]
     L.ksim_pod_add.argtypes = [C.c_void_p, C.c_int64] + podargs

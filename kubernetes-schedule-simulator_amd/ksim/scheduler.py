@@ -565,6 +565,56 @@ class GenericScheduler:
         self.last_scheduled = bound
         return out, ctr, st
 
+    def sweep_drain(self, absent, requeue, first=0, count=None, explain=None):
+        """Drain what-if (ksim_sweep_drain, include/ksim_drain.h): sweep(None, absent=...) with a
+        prefix queue per scenario.  requeue: one list of loaded-queue indices per scenario — the
+        pods re-queued when the scenario's nodes are lost (the requeue_copy of the evicted pods,
+        loaded with the queue); scenario s schedules them in that order on its own copy of the node
+        state, then pods [first, first+count), all from the current lastNodeIndex.  count=0 only
+        re-hosts.  absent None: no node absent in any scenario.  Always the general form
+        (stats.mode == MODE_PERSISTENT, at most abi.SWEEP_GENERAL_MAX_NODES nodes) under this
+        scheduler's own policy; its refusals (sweep) apply to the re-queued pods as well.
+        Returns (placements [n_scen][count], requeued — one int32 array per scenario, the node of
+        each re-queued pod or -1 —, final counters [n_scen], stats); self.last_scheduled /
+        self.last_rehosted hold the pods bound per scenario among the range / the prefix.
+        explain: as in sweep; self.last_failures["pod"] then holds positions in the scenario's own
+        queue (0 .. len(requeue[s])-1 the prefix, len(requeue[s]) + i range pod first + i) and
+        count the failed pods of prefix and range together."""
+        n = len(self._pods)
+        count = n - first if count is None else count
+        requeue = [np.asarray(list(r), np.int64).reshape(-1) for r in requeue]
+        S = len(requeue)
+        mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
+        if mask is not None and len(mask) != S:
+            raise abi.KsimError(abi.E_INVAL, "sweep_drain: %d re-queue lists but %d absent sets" % (S, len(mask)))
+        off = np.zeros(S + 1, np.int64)
+        off[1:] = np.cumsum([len(r) for r in requeue])
+        pod = np.ascontiguousarray(np.concatenate(requeue)) if S and off[-1] else np.zeros(0, np.int64)
+        pre = np.zeros(len(pod), np.int32)
+        rq = abi.SweepRequeue(abi.ptr(off, C.c_int64), abi.ptr(pod, C.c_int64), abi.ptr(pre, C.c_int32))
+        out = np.zeros((S, max(count, 0)), np.int32)
+        ctr = np.zeros(S, np.uint64)
+        bound = np.zeros(S, np.int32)
+        rehosted = np.zeros(S, np.int32)
+        f = fails = None
+        if explain is not None and explain is not False:
+            longest = int(np.diff(off).max()) if S else 0
+            cap = longest + count if explain is True else int(explain)
+            fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
+                         pod=np.full((S, max(cap, 0)), -1, np.int32),
+                         hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
+            f = C.byref(abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
+                                          abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32)))
+        st = abi.Stats()
+        self.h.call("ksim_sweep_drain", abi.vptr(mask), S, C.byref(rq), first, count, abi.vptr(out), abi.vptr(ctr),
+                    abi.vptr(bound), abi.vptr(rehosted), f, C.byref(st))
+        self.last_stats = st
+        self.last_scheduled = bound
+        self.last_rehosted = rehosted
+        if fails is not None:
+            self.last_failures = fails
+        return out, [pre[off[k]:off[k + 1]] for k in range(S)], ctr, st
+
     def evaluate(self, pod):
         """Per-node (fit, reason mask, map score, reduce class) for one loaded pod (no commit)."""
         n = self.cluster.n_nodes
@@ -647,6 +697,29 @@ def absent_mask(n_nodes, sets):
                 raise abi.KsimError(abi.E_INVAL, "absent set %d: node index outside [0, %d)" % (k, n_nodes))
         np.bitwise_or.at(out[k], idx >> 5, np.uint32(1) << (idx & 31).astype(np.uint32))
     return out
+
+
+def default_evictable(pod):
+    """kubectl drain's rule for a running pod (a v1.Pod object): False for a DaemonSet-owned pod
+    (metadata.ownerReferences[].kind == "DaemonSet"), a mirror pod (annotation
+    kubernetes.io/config.mirror) and a pod whose status.phase is Succeeded or Failed.  Such pods die
+    with their node and are not re-queued."""
+    meta = pod.get("metadata") or {}
+    if any((o or {}).get("kind") == "DaemonSet" for o in meta.get("ownerReferences") or ()):
+        return False
+    if "kubernetes.io/config.mirror" in (meta.get("annotations") or {}):
+        return False
+    return (pod.get("status") or {}).get("phase") not in ("Succeeded", "Failed")
+
+
+def requeue_copy(pod):
+    """The copy of an evicted running pod as a controller would recreate it: spec.nodeName removed,
+    status dropped, everything else kept.  The argument is left as it is."""
+    import copy
+    new = copy.deepcopy({k: v for k, v in pod.items() if k != "status"})
+    if isinstance(new.get("spec"), dict):
+        new["spec"].pop("nodeName", None)
+    return new
 
 
 def outage_sets(cluster_or_nodes, by):
@@ -835,6 +908,7 @@ class ClusterCapacity:
             priorities = q if priorities is None else priorities
         self.order = list(reversed(simulation_pods))   # PodQueue.Pop takes the last element
         self.running = list(running_pods)
+        self.nodes = list(nodes)
         # pvs / pvcs / storage_classes: the simulator's listers are empty; other callers may fill them
         names = {n for n, _ in priorities}
         both = {"SelectorSpreadPriority", "ServiceSpreadingPriority"} <= names
@@ -844,11 +918,12 @@ class ClusterCapacity:
                               "priority, with spread listers (one auxiliary spreading priority)")
         # a second spreading priority over the services (include/ksim.h ksim_affinity_tables.aux_*)
         aux = ("service_spreading",) if both else (("service_anti_affinity", saa[0]) if len(saa) == 1 else None)
-        self.cluster = Cluster.from_objects(nodes, running_pods, self.order, pvs=pvs, pvcs=pvcs,
-                                            storage_classes=storage_classes, spread=spread,
-                                            spread_services_only="ServiceSpreadingPriority" in names and not both,
-                                            aux=aux if spread else None,
-                                            service_affinity=svc_aff if "CheckServiceAffinity" in predicates else None)
+        # the listers / policy keywords of the cluster, kept for drain_what_if's second cluster
+        self._cluster_args = dict(pvs=pvs, pvcs=pvcs, storage_classes=storage_classes, spread=spread,
+                                  spread_services_only="ServiceSpreadingPriority" in names and not both,
+                                  aux=aux if spread else None,
+                                  service_affinity=svc_aff if "CheckServiceAffinity" in predicates else None)
+        self.cluster = Cluster.from_objects(nodes, running_pods, self.order, **self._cluster_args)
         self._sched_args = (predicates, priorities, dict(device=device, mode=mode, label_presence=label_presence,
                                                          custom_priorities=custom, service_affinity=svc_aff))
         self.scheduler = GenericScheduler(self.cluster, predicates, priorities, collect_reasons=collect_reasons,
@@ -933,6 +1008,79 @@ class ClusterCapacity:
                 scal = cl.scalar_names.items
                 recs[-1].update(listed=listed, explained=kept, fit_errors=[
                     (pod_names[int(fails["pod"][s, k])],
+                     fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
+                    for k in range(kept)])
+        return recs
+
+    def drain_what_if(self, outages, first=0, count=None, explain=False, evictable=None):
+        """what_if with the pods of the lost nodes re-queued (ksim_sweep_drain): for every outage the
+        evictable running pods bound to its nodes are scheduled first, as the copies a controller
+        would recreate (requeue_copy) and in the order of running_pods, then the queue — one run of
+        the simulator per outage on the snapshot without the outage's nodes and the pods bound to
+        them, all outages in one sweep.  evictable: a predicate over a running pod (default
+        default_evictable, kubectl drain's rule); a pod it rejects vanishes with its node, as every
+        pod does in what_if.  The sweep runs on a cluster of its own — the snapshot's nodes and
+        running pods, the queue followed by the copy of every evictable pod on a node of any outage,
+        built with the constructor's listers and policy — and on a scheduler of its own.  Queues and
+        evicted pods with inter-pod affinity, spread or volume state are refused (KsimUnsupported).
+        first / count select the queue's range as in what_if (count=0: only re-host).
+        Returns one record per outage: dict(name, absent (node count), evicted, rehosted, stranded,
+        requeued [(pod name, node name or None)] in eviction order, scheduled, failed, placements
+        [(pod name, node name or None)] of the queue's range).
+        explain: True, or an int cap per outage — each record gains listed, fit_errors [(pod name,
+        message)] over the outage's whole queue (evicted pods first, under their original names;
+        report.ERR_NO_NODES when the outage leaves no node) and explained, as in what_if."""
+        cl = self.cluster
+        outages = list(outages)
+        if not outages:
+            return []
+        evictable = default_evictable if evictable is None else evictable
+        sets_ = []
+        for name, members in outages:
+            idx = []
+            for m in members:
+                if isinstance(m, str):
+                    if m not in cl.index:
+                        raise abi.KsimError(abi.E_INVAL, "outage %r: no node named %r" % (name, m))
+                    m = cl.index[m]
+                idx.append(int(m))
+            sets_.append(sorted(set(idx)))
+        nq = len(self.order)
+        count = nq - first if count is None else count
+        lost = set().union(*sets_)
+        evicted = []  # (its node's index, the running pod) of every pod some outage re-queues
+        for pod in self.running:
+            node = cl.index.get((pod.get("spec") or {}).get("nodeName"))
+            if node is not None and node in lost and evictable(pod):
+                evicted.append((node, pod))
+        copies = [requeue_copy(pod) for _, pod in evicted]
+        dcl = Cluster.from_objects(self.nodes, self.running, self.order + copies, **self._cluster_args)
+        requeue = [[nq + k for k, (node, _) in enumerate(evicted) if node in set(idx)] for idx in sets_]
+        predicates, priorities, kw = self._sched_args
+        g = GenericScheduler(dcl, predicates, priorities, collect_reasons=False, **kw)
+        try:
+            out, pre, _, _ = g.sweep_drain(sets_, requeue, first, count, explain=explain if explain else None)
+            fails = g.last_failures if explain else None
+        finally:
+            g.close()
+        names = dcl.names
+        pod_names = dcl.pod_names
+        recs = []
+        for s, ((name, _), idx, row, rq, got) in enumerate(zip(outages, sets_, out, requeue, pre)):
+            bound, back = int((row >= 0).sum()), int((got >= 0).sum())
+            recs.append(dict(name=name, absent=len(idx), evicted=len(rq), rehosted=back, stranded=len(rq) - back,
+                             requeued=[(pod_names[q], names[w] if w >= 0 else None) for q, w in zip(rq, got)],
+                             scheduled=bound, failed=len(row) - bound,
+                             placements=[(pn, names[w] if w >= 0 else None)
+                                         for pn, w in zip(pod_names[first:first + len(row)], row)]))
+            if fails is not None:
+                from .report import ERR_NO_NODES
+                listed = int(fails["listed"][s])
+                kept = min(int(fails["count"][s]), fails["pod"].shape[1])
+                scal = dcl.scalar_names.items
+                queue = list(rq) + list(range(first, first + len(row)))  # the outage's own queue, by loaded index
+                recs[-1].update(listed=listed, explained=kept, fit_errors=[
+                    (pod_names[queue[int(fails["pod"][s, k])]],
                      fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
                     for k in range(kept)])
         return recs
