@@ -322,8 +322,16 @@ int ksim_evaluate(ksim_handle* h, int64_t pod, uint8_t* out_fit, uint32_t* out_r
  * exact int64, each scenario with its own copy of every column a commit writes: it accepts
  * nodeName, host ports, node selectors / required node affinity, tolerations, gpu / ephemeral /
  * extended requests, BestEffort pods and the svc_ok table form of CheckServiceAffinity, on at most
- * 38,400 nodes (KSIM_SWEEP_GENERAL_MAX_NODES).  It refuses (KSIM_E_UNSUPPORTED, the reason in
- * ksim_last_error) a pod in the range with inter-pod affinity, spread or volume state, loaded
+ * 38,400 nodes (KSIM_SWEEP_GENERAL_MAX_NODES).  SelectorSpread queues are swept as well: when the
+ * loaded affinity tables hold SelectorSpread state only (spread_pair and its counted pairs: no
+ * affinity / anti-affinity term of any class, no carried term) and at most 512 zones
+ * (KSIM_SWEEP_SPREAD_MAX_ZONES), a pod with an affinity identity or class is accepted, every scenario
+ * counts on its own copy of cnt, made from the handle's current counts, and SelectorSpreadPriority /
+ * ServiceSpreadingPriority reduce over the scenario's fit nodes (maximum count, haveZones and zone
+ * sums change with the absent nodes); the handle's counts are not written.  Scenario weights over
+ * such a range are refused when the handle has a spread weight: they would drop it.  It refuses
+ * (KSIM_E_UNSUPPORTED, the reason in ksim_last_error) a pod in the range with inter-pod affinity
+ * state (terms, carried terms; spread state next to them) or volume state, loaded
  * auxiliary-priority or CheckServiceAffinity lender tables, a pod class with more than
  * KSIM_MAX_RCLASS reduce classes, a node-sharded handle, and scenario weights on a handle whose own
  * policy has a reduce weight (TaintToleration, NodeAffinity) or a NodePreferAvoidPods addend: the

@@ -62,8 +62,10 @@ typedef struct ksim_sweep_requeue {
  * handle.
  *
  * Refusals (KSIM_E_UNSUPPORTED, under this function's name), for the range and for every prefix pod:
- * inter-pod affinity or spread state, volumes, more than KSIM_MAX_RCLASS reduce classes, loaded
- * auxiliary or CheckServiceAffinity lender tables, a node-sharded handle, more than
+ * inter-pod affinity state (SelectorSpread state alone is swept, as ksim_sweep describes: the
+ * re-queued pods of a service count in the scenario's own copy of the counted pairs; more than
+ * KSIM_SWEEP_SPREAD_MAX_ZONES zones are refused), volumes, more than KSIM_MAX_RCLASS reduce classes,
+ * loaded auxiliary or CheckServiceAffinity lender tables, a node-sharded handle, more than
  * KSIM_SWEEP_GENERAL_MAX_NODES nodes.
  *
  * KSIM_E_INVAL: rq == NULL, a NULL off, off[0] != 0, a decreasing off, a NULL pod or out_node with

@@ -32,7 +32,9 @@ typedef struct ksim_sweep_failures {
  * (its message under this function's name), absent == NULL (no node absent), weights == NULL (the
  * handle's own policy), and the handle's own state, counter and error word left untouched.
  * out_node, out_counters and out_scheduled are bit for bit what ksim_sweep_nodes returns for the
- * same arguments: explaining never changes a decision.
+ * same arguments: explaining never changes a decision.  That includes SelectorSpread queues (swept
+ * when the tables hold SelectorSpread state only; inter-pod affinity state is still refused): a
+ * priority never enters a histogram.
  *
  * Histogram.  A failed pod's histogram is FitError.FailedPredicates of the reference run on the
  * reduced snapshot (generic_scheduler.go:51-90): every node the scenario lists adds one to each

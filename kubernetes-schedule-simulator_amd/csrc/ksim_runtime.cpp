@@ -1585,8 +1585,22 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   if (n > KSIM_SWEEP_GENERAL_MAX_NODES)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout of pods that are not "
                                        "resource-only", who, (long long)n, KSIM_SWEEP_GENERAL_MAX_NODES);
-  if (ksim_rt_aff_count(h, first, count))
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state", who);
+  // A pod with affinity state is swept when that state is SelectorSpread's alone (the SPR
+  // instantiations): no affinity / anti-affinity term of any pod class, no term carried by a running
+  // pod, no auxiliary or lender tables, and the zones within the kernel's LDS words.
+  char spr_no[96] = "";
+  if (h->have_aff) {
+    if (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car)
+      snprintf(spr_no, sizeof spr_no, " (the tables hold inter-pod affinity terms: only SelectorSpread state is swept)");
+    else if (ksim_rt_launch_tables(h))
+      snprintf(spr_no, sizeof spr_no, " (auxiliary spreading priority or lender tables are loaded)");
+    else if (h->aff_n_zone > KSIM_SWEEP_SPREAD_MAX_ZONES)
+      snprintf(spr_no, sizeof spr_no, " (%d zones exceed the %d zones of a swept SelectorSpread queue)", h->aff_n_zone,
+               KSIM_SWEEP_SPREAD_MAX_ZONES);
+  }
+  bool spr = ksim_rt_aff_count(h, first, count) > 0;
+  if (spr && spr_no[0])
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state%s", who, spr_no);
   for (int64_t q = first; q < first + count; ++q)
     if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: pod %lld mounts volumes", who, (long long)q);
   if (ksim_rt_launch_tables(h))
@@ -1600,9 +1614,12 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     std::sort(idx.begin(), idx.end());
     idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
     for (int64_t q : idx) {
-      if (ksim_rt_aff_count(h, q, 1))
-        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld carries inter-pod affinity or spread state", who,
-                    (long long)q);
+      if (ksim_rt_aff_count(h, q, 1)) {
+        if (spr_no[0])
+          return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld carries inter-pod affinity or spread state%s", who,
+                      (long long)q, spr_no);
+        spr = true;
+      }
       if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld mounts volumes", who, (long long)q);
       if (ksim_rt_range_wide(h, q, 1))
         return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the class of re-queued pod %lld has more than %d reduce classes", who,
@@ -1613,14 +1630,21 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over pods that are not resource-only would drop the "
                                        "handle's reduce priorities or NodePreferAvoidPods addend (weights = NULL sweeps "
                                        "under the whole configured policy)", who);
+  // the spread weight a spread pod's packed score carries beside the map weights
+  const int64_t wspr = (spr && !c.no_prio) ? c.w[KSIM_W_SELECTOR_SPREAD] : 0;
+  if (weights && wspr)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over a SelectorSpread queue would drop the handle's "
+                                       "spread priority (weights = NULL sweeps under the whole configured policy)", who);
   std::vector<int64_t> w3(weights ? (size_t)n_scen * 3 : 0);
   for (int32_t sidx = 0; sidx < (weights ? n_scen : 1); ++sidx) {
     const int64_t* w = weights ? weights + (size_t)sidx * KSIM_NW : c.w;
     if (weights && (w[KSIM_W_TAINT_TOLERATION] || w[KSIM_W_NODE_AFFINITY]))
       return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: reduce priorities are not swept", who, sidx);
-    // a packed evaluation holds the map score in KSIM_SWEEP_GENERAL_SCORE_BITS bits
-    int64_t tot = 0;
+    // a packed evaluation holds the map score (and a spread pod's spread score) in
+    // KSIM_SWEEP_GENERAL_SCORE_BITS bits: 10 x (LeastRequested + MostRequested + Balanced + spread weight)
     const int64_t lim = ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10;
+    if (wspr < 0 || wspr >= lim) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
+    int64_t tot = wspr;
     for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED}) {
       if (w[k] < 0 || w[k] >= lim) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
       tot += w[k];
@@ -1646,14 +1670,17 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
   const size_t b_w = weights ? al(S * 24) : 0;
   // the prefix queues of the whole sweep (off, pod, out_pre): uploaded once, indexed by global scenario
   const size_t b_rq = rq ? al((S + 1) * 8) + al(T * 8) + al(T * 4) : 0;
+  // a SelectorSpread queue: a scenario's copy of the counted pairs and its affinity descriptor
+  const size_t CL = spr ? (size_t)h->aff_cnt_len : 0;
+  const size_t spr_per = spr ? CL * 4 + sizeof(KsimAff) : 0;
   auto need_of = [&](size_t C) {
     return 6 * al(C * N * 8) + 3 * al(C * N * 4) + al(C * N * NS * 8) + al(C * N * NP * 8) + al(C * sizeof(KsimCtx)) + b_w +
            al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0) + (wcap ? al(C * wcap * 4) + al(C * why_bytes(wcap) - C * wcap * 4) : 0) +
-           b_rq;
+           b_rq + (spr ? al(C * CL * 4) + al(C * sizeof(KsimAff)) : 0);
   };
   size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
   if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
-  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW + why_bytes(wcap);
+  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW + why_bytes(wcap) + spr_per;
   budget = budget > b_rq ? budget - b_rq : 0;
   int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
   if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
@@ -1714,6 +1741,13 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     HIPCHK(h, hipMemcpyAsync(doff, rq->off, (S + 1) * 8, hipMemcpyHostToDevice, ksim_stream(h)));
     if (T) HIPCHK(h, hipMemcpyAsync(dpod, rq->pod, T * 8, hipMemcpyHostToDevice, ksim_stream(h)));
   }
+  SwgSpread sprd{};
+  if (spr) {  // every launch copies the handle's current counts: the handle's own are only read
+    sprd.base = h->aff_h;
+    sprd.cnt_len = (int64_t)CL;
+    sprd.cnt = (int32_t*)take(C * CL * 4);
+    sprd.aff = (KsimAff*)take(C * sizeof(KsimAff));
+  }
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
@@ -1723,8 +1757,9 @@ static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights
     a.scen0 = s0;  // the chunk's first scenario: its row of the weights
     if (absent)
       HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
-    hipError_t e = rq ? ksim_sweep_drain_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h))
-                      : ksim_sweep_general_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h));
+    hipError_t e = spr  ? ksim_sweep_spread_launch(&c, &cols, &a, &sprd, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h))
+                   : rq ? ksim_sweep_drain_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h))
+                        : ksim_sweep_general_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h));
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
     HIPCHK(h, hipEventSynchronize(h->ev1));
     float c_ms = 0.f;

@@ -75,9 +75,32 @@ struct SwgArgsPre : SwgArgsWhy {
   int32_t* out_pre;    // [off[S]]
 };
 
+// SelectorSpread queues (the SPR instantiations): a range or prefix pod with SelectorSpread state,
+// on tables that hold nothing else.  Scenario s of a chunk owns the s-th [cnt_len] copy of the
+// counted-pair array (made from the handle's current counts, so a schedule() of a prefix is carried)
+// and a KsimAff of its own with cnt rebased to it; aff[s] is read beside the scenario's KsimCtx, whose
+// aff stays null for the predicates (with spread-only tables MatchInterPodAffinity is vacuous).
+struct SwgArgsSpr : SwgArgsPre {
+  const KsimAff* aff;  // [C] the scenarios' tables; off == null: no prefix queues
+};
+// What the launcher needs for them: the handle's tables, the chunk's count copies and descriptors.
+struct SwgSpread {
+  KsimAff base;     // the handle's descriptor (host copy)
+  int32_t* cnt;     // [C][cnt_len]
+  int64_t cnt_len;
+  KsimAff* aff;     // [C]
+};
+
 // one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
 #define KSIM_SWEEP_GENERAL_MAX_NODES 38400
 #define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word
+// countsByZone of the current and the next pod as 64-bit LDS words (2 x 512 x 8 B = 8 KiB beside the
+// 150 KiB of evaluations and the 1 KiB of reduction words, within the 160 KiB of a workgroup).  A word
+// sums int32 counts over at most KSIM_SWEEP_GENERAL_MAX_NODES nodes: below 2^47, no overflow.
+#define KSIM_SWEEP_SPREAD_MAX_ZONES 512
+static_assert(KSIM_SWEEP_GENERAL_MAX_NODES * 4 + 2 * KSIM_SWEEP_SPREAD_MAX_ZONES * 8 + 1024 <= 160 * 1024,
+              "evaluations + zone words + reduction words exceed a workgroup's LDS");
 static_assert(KSIM_MAX_RCLASS <= 16, "the reduce class takes the low four bits of a packed evaluation");
 static_assert(sizeof(KsimCtx) + sizeof(SwgArgsWhy) <= 4096 - 64, "KsimCtx + SwgArgs exceed the kernel-argument limit");
 static_assert(sizeof(KsimCtx) + sizeof(SwgArgsPre) <= 4096 - 64, "KsimCtx + SwgArgsPre exceed the kernel-argument limit");
+static_assert(sizeof(KsimCtx) + sizeof(SwgArgsSpr) <= 4096 - 64, "KsimCtx + SwgArgsSpr exceed the kernel-argument limit");

@@ -221,6 +221,18 @@ struct SwgAcc {
   __device__ __forceinline__ int tt_class(const ksim_pod&, int64_t) const { return ttc; }
   __device__ __forceinline__ int na_class(const ksim_pod&, int64_t) const { return nac; }
 };
+
+// LDS of the SPR instantiations only: countsByZone of the pod (buffer = the step's parity, the other
+// one is reset between two barriers, as the class words are), and the second block reduction's words.
+struct SwgSpreadLds {
+  unsigned long long z[2][KSIM_SWEEP_SPREAD_MAX_ZONES];
+  int32_t red[SW][2];
+};
+__device__ __forceinline__ SwgSpreadLds& swg_spread_lds() {
+  __shared__ SwgSpreadLds l;
+  return l;
+}
+constexpr int SWG_AGG_ZONES = 16;  // up to here a wave adds one sum per zone it holds, not one per lane
 }  // namespace
 
 // WHY (ksim_sweep_explain): as in the scan form, the reason masks from ksim_predicates_a.  The packed
@@ -233,10 +245,24 @@ struct SwgAcc {
 // the range's steps do, not with index -> record -> class tables in a row.  The class words'
 // buffer is the parity of q: the range's own index would repeat the last prefix step's buffer at an
 // odd m.  A record of why holds q.
-template <bool ABS, bool WHY, bool PRE = false>
+//
+// SPR (a range or prefix pod with SelectorSpread state; the tables hold nothing else): a pod whose
+// class has a spread pair scores CalculateSpreadPriorityReduce (selector_spreading.go:121-174) over the
+// scenario's fit nodes.  Step 1 also loads each fit row's count and zone, keeps the maximum count and
+// haveZones, and adds the count to the zone's LDS word; its packed word holds the map score alone, and
+// neither (M, C) nor a class maximum is taken from it.  After the block reduction of (F, maximum
+// count, haveZones) every wave takes the maximum zone word, and each thread revisits its own rows
+// (the same j = tid + k * 1024, so its own words: no barrier on sg), adds weight x ksim_spread_score,
+// rewrites the word and only then takes (M, C) or the class maximum; one more barrier publishes them.
+// The count and zone are reloaded there, not kept: the kernel has no registers to spare.  The
+// committing thread also runs ksim_aff_commit_body on the scenario's counts, for every pod with an
+// identity.  Barriers per pod: 3 with one reduce class and 4 with several, as ever; a pod that reads a
+// spread pair takes one more (4 and 5).  A pod without a pair scores a constant: today's steps.
+template <bool ABS, bool WHY, bool PRE = false, bool SPR = false>
 __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
     const KsimCtx* __restrict__ ctxs,
-    const std::conditional_t<PRE, SwgArgsPre, std::conditional_t<WHY, SwgArgsWhy, SwgArgs>> a) {
+    const std::conditional_t<SPR, SwgArgsSpr,
+                             std::conditional_t<PRE, SwgArgsPre, std::conditional_t<WHY, SwgArgsWhy, SwgArgs>>> a) {
   extern __shared__ uint32_t sg[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
   __shared__ int32_t s_wtot[SW];
@@ -256,6 +282,18 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
   if (tid < 2 * KSIM_MAX_RCLASS) {
     (&s_M[0][0])[tid] = -1;
     (&s_C[0][0])[tid] = 0;
+  }
+  // SPR: the scenario's tables, its zone row and zone count (uniform), both buffers of zone words
+  const KsimAff* Ap = nullptr;
+  const int32_t* zrow = nullptr;
+  int32_t nz = 0;
+  if constexpr (SPR) {
+    Ap = a.aff + s;
+    if (Ap->zone_key >= 0) {
+      zrow = Ap->dom + (int64_t)Ap->zone_key * n;
+      nz = Ap->n_zone;  // <= KSIM_SWEEP_SPREAD_MAX_ZONES (host-checked)
+    }
+    for (int z = tid; z < 2 * KSIM_SWEEP_SPREAD_MAX_ZONES; z += SB) (&swg_spread_lds().z[0][0])[z] = 0;
   }
   __syncthreads();
   // PRE: the scenario's prefix pre[0 .. m) and the queue index of its step q (uniform)
@@ -301,6 +339,16 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       av = c.na_val[(int64_t)P.cls * c.val_w + lane % k2];
       ad = c.na_add ? c.na_add[(int64_t)P.cls * c.val_w + lane % k2] : 0;
     }
+    // SPR: the pod's SelectorSpread pair (uniform; -1: none, a constant score), the scenario's counts
+    // of it per node, the zone words of this step and the thread's maximum count / haveZones
+    int32_t sp = -1, mxc = 0, hzt = 0;
+    const int32_t* scnt = nullptr;
+    unsigned long long* zw = nullptr;
+    if constexpr (SPR) {
+      if (c.w[KSIM_W_SELECTOR_SPREAD] != 0 && !c.no_prio) sp = ksim_spread_pair(*Ap, P);
+      if (sp >= 0) scnt = Ap->cnt + Ap->pair_off[sp];
+      zw = swg_spread_lds().z[pb];
+    }
     // ---- 1. evaluate every row ----
     int32_t f = 0, mx = -1, cm = 0;
     for (int64_t j = tid; j < n; j += SB) {
@@ -317,6 +365,13 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
         if (k1 > 1) acc.ttc = c.tt_class[cl * c.n_taint_sets + ts];
         if (k2 > 1) acc.nac = c.na_class[cl * c.n_label_sets + ls];
       }
+      int32_t cv = 0, zj = -1;  // SPR: the row's count and zone, loaded with the row (used when it fits)
+      if constexpr (SPR) {
+        if (sp >= 0) {
+          cv = scnt[j];
+          if (zrow) zj = zrow[j];
+        }
+      }
       bool fit = true;
       if constexpr (ABS) fit = r.count >= 0;  // a node this scenario does not list
       if (fit) fit = ksim_predicates_a<SwgAcc, true, true>(c, P, j, r, acc) == 0;
@@ -326,7 +381,9 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
         int q = 0;
         if (K > 1) {
           q = ksim_rclass_a(P, j, k1, k2, acc);
-          if (e > __hip_atomic_load(&s_M[pb][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&s_M[pb][q], e);
+          // (SPR, a spread pod: the score is incomplete, the class maximum is taken in step 1b)
+          if ((!SPR || sp < 0) && e > __hip_atomic_load(&s_M[pb][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+            atomicMax(&s_M[pb][q], e);
         }
         wd = ((uint32_t)e << 4) | (uint32_t)q;
         f += 1;
@@ -334,6 +391,27 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
         mx = e > mx ? e : mx;
       }
       sg[j] = wd;
+      if constexpr (SPR) {
+        if (sp >= 0) {  // uniform
+          mxc = (fit && cv > mxc) ? cv : mxc;
+          hzt |= (fit && zj >= 0) ? 1 : 0;
+          const int64_t add = (fit && zj >= 0) ? (int64_t)cv : 0;
+          // the wave's rows of this round are j - lane .. j - lane + 63: all below n = every lane is here
+          if (nz <= SWG_AGG_ZONES && j - lane + 64 <= n) {
+            uint64_t m = __ballot(add != 0);
+            while (m) {  // uniform: one step, one wave sum and one LDS add per zone among the wave's counts
+              const int l = __builtin_ctzll(m);
+              const int32_t zl = __builtin_amdgcn_readlane(zj, l);
+              const bool mine = add != 0 && zj == zl;
+              const int64_t tot = ksimw::sum_i64(mine ? add : 0);
+              if (lane == l) atomicAdd(&zw[zl], (unsigned long long)tot);
+              m &= ~__ballot(mine);
+            }
+          } else if (add != 0) {
+            atomicAdd(&zw[zj], (unsigned long long)add);
+          }
+        }
+      }
     }
     // ---- 2. block reduction: F, and for one class M, C ----
     {
@@ -341,16 +419,25 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       const int32_t Mw = ksimw::max_i32(mx);
       const int32_t Cw = ksimw::sum_i32((mx == Mw && mx >= 0) ? cm : 0);
       if (lane == 0) { s_red[wv][0] = Fw; s_red[wv][1] = Mw; s_red[wv][2] = Cw; }
+      if constexpr (SPR) {
+        if (sp >= 0) {  // a spread pod: the maximum count and haveZones in place of (M, C)
+          const int32_t Xw = ksimw::max_i32(mxc), Hw = ksimw::max_i32(hzt);
+          if (lane == 0) { s_red[wv][1] = Xw; s_red[wv][2] = Hw; }
+        }
+      }
     }
     __syncthreads();
     if (tid < KSIM_MAX_RCLASS) {  // the next pod's class words
       s_M[pb ^ 1][tid] = -1;
       s_C[pb ^ 1][tid] = 0;
     }
+    if constexpr (SPR) {
+      if (tid < nz) swg_spread_lds().z[pb ^ 1][tid] = 0;  // ... and its zone words
+    }
     const bool in = lane < SW;
     const int32_t F = ksimw::sum_i32(in ? s_red[in ? lane : 0][0] : 0);
     const int32_t mw = in ? s_red[lane][1] : -1;
-    const int32_t M = ksimw::max_i32(mw);
+    int32_t M = ksimw::max_i32(mw);
     int32_t C = ksimw::sum_i32((in && mw == M && M >= 0) ? s_red[lane][2] : 0);
     if (F == 0) {  // FitError: no node fits
       if (tid == 0) *answer_of(p) = -1;
@@ -389,6 +476,46 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       }
       __syncthreads();  // s_red (and s_hist) are rewritten by the next pod
       continue;
+    }
+    if constexpr (SPR) {
+      if (sp >= 0) {  // ---- 1b. the spread score of the thread's own fit rows, then (M, C) or the class maxima ----
+        const int64_t max_node = (int64_t)ksimw::max_i32(in ? s_red[lane][1] : 0);
+        const bool have_zones = ksimw::max_i32(in ? s_red[lane][2] : 0) != 0;
+        unsigned long long zm = 0;  // every wave: the maximum over all zone words (zones without a fit node hold 0)
+        for (int z = lane; z < nz; z += 64) zm = zw[z] > zm ? zw[z] : zm;
+        const int64_t max_zone = ksimw::max_i64((int64_t)zm);
+        const int32_t wsp = (int32_t)c.w[KSIM_W_SELECTOR_SPREAD];
+        mx = -1;
+        cm = 0;
+        for (int64_t j = tid; j < n; j += SB) {
+          const uint32_t wd = sg[j];
+          if (wd == GNOFIT) continue;
+          const int32_t zj = zrow ? zrow[j] : -1;
+          const int64_t zs = zj >= 0 ? (int64_t)zw[zj] : 0;
+          // < 2^27 with the map score (host-checked weights)
+          const int32_t e = (int32_t)(wd >> 4) + wsp * (int32_t)ksim_spread_score(scnt[j], max_node, have_zones, zj, zs, max_zone);
+          const uint32_t q = wd & 15u;
+          sg[j] = ((uint32_t)e << 4) | q;
+          if (K > 1) {
+            if (e > __hip_atomic_load(&s_M[pb][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&s_M[pb][q], e);
+          } else {
+            cm = e > mx ? 1 : cm + (e == mx ? 1 : 0);
+            mx = e > mx ? e : mx;
+          }
+        }
+        int32_t (*red)[2] = swg_spread_lds().red;
+        if (K == 1) {
+          const int32_t Mw = ksimw::max_i32(mx);
+          const int32_t Cw = ksimw::sum_i32((mx == Mw && mx >= 0) ? cm : 0);
+          if (lane == 0) { red[wv][0] = Mw; red[wv][1] = Cw; }
+        }
+        __syncthreads();
+        if (K == 1) {
+          const int32_t mw2 = in ? red[lane][0] : -1;
+          M = ksimw::max_i32(mw2);
+          C = ksimw::sum_i32((in && mw2 == M && M >= 0) ? red[lane][1] : 0);
+        }
+      }
     }
     uint32_t win = 1u;
     if (K > 1) {
@@ -443,6 +570,9 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
         }
       }
       if (jsel >= 0) ksim_commit(c, P, jsel);
+      if constexpr (SPR) {  // NodeInfo.AddPod on the scenario's counts: every pod with an identity
+        if (jsel >= 0) ksim_aff_commit_body(*Ap, P, jsel, +1);
+      }
       *answer_of(p) = (int32_t)jsel;
     }
     __syncthreads();  // the commit (workgroup release/acquire) before the next pod's loads
@@ -485,6 +615,19 @@ __global__ void ksim_sweep_general_init_kernel(SwgCols src, SwgCols d, int64_t n
   d.pod_count[k] = src.pod_count[i]; d.port_count[k] = src.port_count[i]; d.flags[k] = src.flags[i];
   for (int32_t t = 0; t < n_scalar; ++t) d.req_scalar[(s * n_scalar + t) * n + i] = src.req_scalar[(int64_t)t * n + i];
   for (int32_t t = 0; t < port_slots; ++t) d.ports[(s * port_slots + t) * n + i] = src.ports[(int64_t)t * n + i];
+}
+
+// SPR: every scenario's copy of the counted pairs from the handle's current counts, and its tables:
+// the handle's descriptor with cnt at the copy (nothing else of it is written by the sweep)
+__global__ void ksim_sweep_spread_init_kernel(const KsimAff base, int32_t* cnt, int64_t cnt_len, int64_t total,
+                                              int32_t n_scen, KsimAff* out) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < total) cnt[k] = base.cnt[k % cnt_len];
+  if (k < n_scen) {
+    KsimAff& A = out[k];
+    A = base;
+    A.cnt = cnt + k * cnt_len;
+  }
 }
 
 // static float64 columns, once per handle
@@ -564,10 +707,16 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
 // The general form: hc the handle's context, cols the chunk's scenario columns, err the sweep's own
 // error word (ksim_commit's port-slot overflow bit; the handle's word is never written).
 // args->off set: the PRE instantiations (ksim_sweep_drain).
+// spr set: the SPR instantiations (a SelectorSpread queue).
 static hipError_t swg_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args, int32_t n_scen,
                              const uint32_t* absent, int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                             hipStream_t st) {
+                             hipStream_t st, const SwgSpread* spr = nullptr) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
+  if (spr) {
+    const int64_t ct = spr->cnt_len * (int64_t)n_scen, thr = ct > n_scen ? ct : (int64_t)n_scen;
+    hipLaunchKernelGGL(ksim_sweep_spread_init_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st, spr->base,
+                       spr->cnt, spr->cnt_len, ct, n_scen, spr->aff);
+  }
   SwgCols src{hc->req_cpu, hc->req_mem, hc->req_gpu, hc->req_eph, hc->nz_cpu, hc->nz_mem,
               hc->req_scalar, hc->ports, hc->pod_count, hc->port_count, hc->flags};
   hipLaunchKernelGGL(ksim_sweep_general_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, *cols, n,
@@ -589,7 +738,17 @@ static hipError_t swg_launch(const KsimCtx* hc, const SwgCols* cols, const SwgAr
   const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
   const KsimCtx* ctx = args->ctx;
   const dim3 grid((unsigned)n_scen), block(SB);
-  if (args->off) {  // ksim_sweep_drain
+  if (spr) {
+    // two instantiations, with and without prefix queues: ABS and WHY are on in both (without node
+    // sets no count is negative, without records why.cap is 0: the same answers)
+    SwgArgsSpr sa{};
+    (SwgArgsPre&)sa = *args;
+    sa.aff = spr->aff;
+    if (args->off)
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, true, true>), grid, block, lds, st, ctx, sa);
+    else
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, false, true>), grid, block, lds, st, ctx, sa);
+  } else if (args->off) {  // ksim_sweep_drain
     if (absent && why)
       hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, true>), grid, block, lds, st, ctx, *args);
     else if (absent)
@@ -625,4 +784,14 @@ extern "C" hipError_t ksim_sweep_drain_launch(const KsimCtx* hc, const SwgCols* 
                                               int32_t n_scen, const uint32_t* absent, int32_t absent_words,
                                               int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   return swg_launch(hc, cols, args, n_scen, absent, absent_words, err, ev0, ev1, st);
+}
+
+// The general form over a SelectorSpread queue (the SPR instantiations): spr holds the handle's
+// affinity descriptor and the chunk's count copies and per-scenario descriptors; args->off set: with
+// prefix queues (ksim_sweep_drain).
+extern "C" hipError_t ksim_sweep_spread_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
+                                               const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
+                                               int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
+                                               hipStream_t st) {
+  return swg_launch(hc, cols, args, n_scen, absent, absent_words, err, ev0, ev1, st, spr);
 }

@@ -20,6 +20,8 @@ MAX_RCLASS = 16
 MAX_WIDE = 256  # reduce classes per pod (KSIM_MAX_WIDE)
 # node cap of the scenario sweep's general form (KSIM_SWEEP_GENERAL_MAX_NODES, csrc/ksim_sweep.h)
 SWEEP_GENERAL_MAX_NODES = 38400
+# zone cap of a swept SelectorSpread queue (KSIM_SWEEP_SPREAD_MAX_ZONES, csrc/ksim_sweep.h)
+SWEEP_SPREAD_MAX_ZONES = 512
 NREASONS = 32
 
 # predicate bits

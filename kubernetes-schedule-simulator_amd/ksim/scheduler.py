@@ -476,8 +476,13 @@ class GenericScheduler:
         abi.SWEEP_GENERAL_MAX_NODES nodes): pods with nodeName, host ports, node selectors /
         required node affinity, tolerations, gpu / ephemeral / extended requests, BestEffort pods,
         and with scenarios=None the whole configured policy (TaintToleration, NodeAffinity,
-        NodePreferAvoidPods, the constants).  Still refused (KsimUnsupported): a pod in the range
-        with inter-pod affinity, spread or volume state, an auxiliary spreading priority or
+        NodePreferAvoidPods, the constants).  SelectorSpread queues are swept too: on a cluster
+        built with SpreadListers whose tables hold spread state only (no pod anywhere with inter-pod
+        affinity terms, at most abi.SWEEP_SPREAD_MAX_ZONES zones) every scenario counts the pods of
+        a service or controller on its own copy of the counts, and SelectorSpreadPriority /
+        ServiceSpreadingPriority reduce over the scenario's fit nodes; scenarios=None only, when the
+        policy has a spread weight.  Still refused (KsimUnsupported): a pod in the range
+        with inter-pod affinity or volume state, an auxiliary spreading priority or
         CheckServiceAffinity with services selecting the pods, more than abi.MAX_RCLASS reduce
         classes in a pod class, a node-sharded scheduler, a scenario with a reduce priority, and
         explicit scenarios over such a queue when this scheduler's own policy has a reduce
@@ -573,7 +578,8 @@ class GenericScheduler:
         state, then pods [first, first+count), all from the current lastNodeIndex.  count=0 only
         re-hosts.  absent None: no node absent in any scenario.  Always the general form
         (stats.mode == MODE_PERSISTENT, at most abi.SWEEP_GENERAL_MAX_NODES nodes) under this
-        scheduler's own policy; its refusals (sweep) apply to the re-queued pods as well.
+        scheduler's own policy; its refusals (sweep) apply to the re-queued pods as well, and so does
+        what it accepts: re-queued pods of a service or controller are swept under SelectorSpread.
         Returns (placements [n_scen][count], requeued — one int32 array per scenario, the node of
         each re-queued pod or -1 —, final counters [n_scen], stats); self.last_scheduled /
         self.last_rehosted hold the pods bound per scenario among the range / the prefix.
@@ -964,8 +970,9 @@ class ClusterCapacity:
         with it: nothing is re-queued.  The sweep starts from the snapshot as loaded (not from the
         state a run() left), on a scheduler of its own.  Queues with node selectors, tolerations,
         host ports, nodeName and gpu / ephemeral / extended requests are swept under the whole
-        provider or policy; queues with inter-pod affinity, spread or volume state are refused
-        (KsimUnsupported), as by GenericScheduler.sweep.
+        provider or policy, and with spread= listers under SelectorSpreadPriority /
+        ServiceSpreadingPriority, reduced over each outage's own fit nodes; queues with inter-pod
+        affinity or volume state are refused (KsimUnsupported), as by GenericScheduler.sweep.
         Returns one record per outage: dict(name, absent (node count), scheduled, failed,
         placements [(pod name, node name or None)] in queue order).
         explain (ksim_sweep_explain): True, or an int cap per outage — each record gains listed (the
@@ -1021,8 +1028,10 @@ class ClusterCapacity:
         default_evictable, kubectl drain's rule); a pod it rejects vanishes with its node, as every
         pod does in what_if.  The sweep runs on a cluster of its own — the snapshot's nodes and
         running pods, the queue followed by the copy of every evictable pod on a node of any outage,
-        built with the constructor's listers and policy — and on a scheduler of its own.  Queues and
-        evicted pods with inter-pod affinity, spread or volume state are refused (KsimUnsupported).
+        built with the constructor's listers and policy — and on a scheduler of its own.  With spread=
+        listers the evicted pods of a service or controller are re-hosted under the spread priority, as
+        the queue is.  Queues and evicted pods with inter-pod affinity or volume state are refused
+        (KsimUnsupported).
         first / count select the queue's range as in what_if (count=0: only re-host).
         Returns one record per outage: dict(name, absent (node count), evicted, rehosted, stranded,
         requeued [(pod name, node name or None)] in eviction order, scheduled, failed, placements
