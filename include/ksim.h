@@ -651,6 +651,16 @@ int ksim_read_nodes(ksim_handle* h, ksim_node_state* out);
 int ksim_get_counter(ksim_handle* h, uint64_t* out);
 int ksim_set_counter(ksim_handle* h, uint64_t value);
 
+/* Form of the dominant kernel of the last ksim_schedule call (diagnostic, handle state only):
+ * KSIM_FORM_FAST = the specialised resource-only persistent kernel, with KSIM_FORM_STREAM when its
+ * rows streamed from HBM and KSIM_FORM_CACHED when it kept per-class evaluations in LDS; bits 8-15
+ * hold its rows per row thread (1, 2, 4 or 9).  0 for every other kernel and before any call. */
+#define KSIM_FORM_FAST 1
+#define KSIM_FORM_STREAM 2
+#define KSIM_FORM_CACHED 4
+#define KSIM_FORM_ROWS_SHIFT 8
+int ksim_last_form(ksim_handle* h, int32_t* form);
+
 /* Device self-test of the wave64 DPP reduction/scan helpers the kernels use (diagnostic):
  * returns the number of mismatching lanes against plain lane loops (0 = pass, <0 = error). */
 int ksim_selftest(void);

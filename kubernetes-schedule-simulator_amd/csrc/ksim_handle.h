@@ -60,6 +60,7 @@ extern "C" size_t ksim_pfast_granule_bytes(void);
 extern "C" size_t ksim_shard_xchg_bytes(void);
 extern "C" size_t ksim_shard_lx_offset(void);
 extern "C" size_t ksim_pfast_cache_bytes(int lds_rows, int ncls);
+extern "C" int ksim_pfast_rows_per_thread(int lds_rows, int stream);
 extern "C" hipError_t ksim_launch_pfast(const KsimCtx* c, uint64_t* granules, int grid, int lds_rows, double* mirror,
                                         const KsimShard* sh, const int32_t* tcls, const KsimTreeClass* tclass, int ncls,
                                         hipStream_t s);
@@ -172,6 +173,7 @@ struct ksim_handle {
   // node table (any other commit path clears it)
   int32_t n_tcls = 0;                      // -1: more classes than the tree supports
   bool last_pfast_cache = false;           // the last fast-kernel call took the cached form
+  int32_t last_form = 0;                   // KSIM_FORM_* of the last ksim_schedule call (ksim_last_form)
   uint64_t* pick_words = nullptr;          // the per-pod pick kernel's exchange records
   uint32_t pick_tag = 0;
   int pick_grid = -1, pick_npt = -1;

@@ -1040,6 +1040,11 @@ extern "C" size_t ksim_pfast_cache_bytes(int lds_rows, int ncls) {
   return (size_t)lds_rows * LDS_ROW_BYTES + b <= (size_t)PF_LDS_BUDGET ? b : 0;
 }
 
+// rows per row thread of the instantiation ksim_launch_pfast picks (the same thresholds)
+extern "C" int ksim_pfast_rows_per_thread(int lds_rows, int stream) {
+  return lds_rows <= RT ? 1 : lds_rows <= 2 * RT ? 2 : (lds_rows <= 4 * RT || !stream) ? 4 : 9;
+}
+
 extern "C" hipError_t ksim_launch_pfast(const KsimCtx* c, uint64_t* granules, int grid, int lds_rows, double* mirror,
                                         const KsimShard* sh, const int32_t* tcls, const KsimTreeClass* tclass, int ncls,
                                         hipStream_t s) {

@@ -800,11 +800,14 @@ static int run_pfast_mode(ksim_handle* h, int64_t first, int64_t count, int grid
     if (sw < 32767 && ksim_pfast_cache_bytes(lds_rows, h->n_tcls)) ncls = h->n_tcls;
   }
   h->last_pfast_cache = ncls > 0;
+  h->last_form = KSIM_FORM_FAST | (stream ? KSIM_FORM_STREAM : 0) | (ncls > 0 ? KSIM_FORM_CACHED : 0) |
+                 (ksim_pfast_rows_per_thread(lds_rows, stream ? 1 : 0) << KSIM_FORM_ROWS_SHIFT);
   HIPCHK(h, hipMemsetAsync(h->granules, 0, gb, ksim_stream(h)));
   HIPCHK(h, hipEventRecord(h->ev0, ksim_stream(h)));
   hipError_t e = ksim_launch_pfast(&c, h->granules, grid, lds_rows, stream ? h->mirror : nullptr, &h->shard, h->tcls,
                                    h->tclass, ncls, ksim_stream(h));
   if (e == hipErrorCooperativeLaunchTooLarge) {
+    h->last_form = 0;
     // the grid cannot be co-resident here (a smaller or shared device): the general kernels instead
     if (h->cfg.mode != KSIM_MODE_PERSISTENT && h->shard.world == 1) {
       h->pfast_off = true;
@@ -1343,6 +1346,7 @@ int ksim_schedule(ksim_handle* h, int64_t first, int64_t count, int32_t* out_nod
   if (first < 0 || count < 0 || first + count > h->n_pods) return ksim_fail(h, KSIM_E_INVAL, "ksim_schedule: range out of bounds");
   HIPCHK(h, hipSetDevice(h->device));
   if (st) memset(st, 0, sizeof *st);
+  h->last_form = 0;
   if (count == 0) return KSIM_OK;
   KsimCtx& c = h->ctx;
   if (c.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
@@ -1839,18 +1843,20 @@ static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, c
     w3[3 * sidx + 1] = (int32_t)w[KSIM_W_MOST_REQUESTED];
     w3[3 * sidx + 2] = (int32_t)w[KSIM_W_BALANCED];
   }
-  // float64 exactness: node quantities + count x the largest pod quantity stay below 2^48
+  // float64 exactness: capacities below 2^48 (they never grow), and the requested quantities +
+  // count x the largest pod quantity stay below 2^48
   {
-    int64_t qmax = 0, nmax = 0;
+    int64_t qmax = 0, nmax = 0, amax = 0;
     for (int64_t i = first; i < first + count; ++i) qmax = std::max(qmax, h->pod_qmax[i]);
     std::vector<int64_t> col((size_t)n);
     for (const int64_t* d : {c.alloc_cpu, c.alloc_mem, (const int64_t*)c.req_cpu, (const int64_t*)c.req_mem,
                              (const int64_t*)c.nz_cpu, (const int64_t*)c.nz_mem}) {
       HIPCHK(h, hipMemcpy(col.data(), d, (size_t)n * 8, hipMemcpyDeviceToHost));
-      for (int64_t v : col) nmax = std::max(nmax, v < 0 ? INT64_MAX / 2 : v);
+      int64_t& mx = (d == c.alloc_cpu || d == c.alloc_mem) ? amax : nmax;
+      for (int64_t v : col) mx = std::max(mx, v < 0 ? INT64_MAX / 2 : v);
     }
     const int64_t lim = (int64_t)1 << 48;
-    if (nmax >= lim || qmax >= lim || count > lim / std::max<int64_t>(qmax, 1) || nmax + count * qmax >= lim)
+    if (amax >= lim || nmax >= lim || qmax >= lim || count > lim / std::max<int64_t>(qmax, 1) || nmax + count * qmax >= lim)
       return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: quantities may leave the exact float64 range (2^48)", who);
   }
   int rc;
@@ -2238,6 +2244,12 @@ int ksim_read_nodes(ksim_handle* h, ksim_node_state* o) {
     HIPCHK(h, hipMemcpy(o->req_scalar, c.req_scalar, (size_t)c.n_scalar * n * 8, hipMemcpyDeviceToHost));
   if (o->ports && c.port_slots) HIPCHK(h, hipMemcpy(o->ports, c.ports, (size_t)c.port_slots * n * 8, hipMemcpyDeviceToHost));
   if (o->port_count) HIPCHK(h, hipMemcpy(o->port_count, c.port_count, n * 4, hipMemcpyDeviceToHost));
+  return KSIM_OK;
+}
+
+int ksim_last_form(ksim_handle* h, int32_t* form) {
+  if (!h || !form) return ksim_fail(h, KSIM_E_INVAL, "ksim_last_form: null argument");
+  *form = h->last_form;
   return KSIM_OK;
 }
 

@@ -203,7 +203,9 @@ EXPORTS = ["ksim_abi_version", "ksim_last_error", "ksim_create", "ksim_destroy",
            "ksim_shard_setup", "ksim_shard_export", "ksim_shard_connect", "ksim_shard_connect_local",
            "ksim_schedule_one", "ksim_pod_add", "ksim_pod_remove", "ksim_node_add", "ksim_node_update",
            "ksim_node_remove", "ksim_node_count", "ksim_append_pods", "ksim_load_affinity", "ksim_load_volumes",
-           "ksim_read_volumes", "ksim_grow_volumes", "ksim_sweep_nodes"]
+           "ksim_read_volumes", "ksim_grow_volumes", "ksim_sweep_nodes", "ksim_last_form"]
+# ksim_last_form bits (include/ksim.h)
+FORM_FAST, FORM_STREAM, FORM_CACHED, FORM_ROWS_SHIFT = 1, 2, 4, 8
 IPC_HANDLE_BYTES = 64
 MAX_RANKS = 8
 
@@ -249,6 +251,7 @@ def lib():
     L.ksim_get_counter.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.ksim_set_counter.argtypes = [C.c_void_p, C.c_uint64]
     L.ksim_selftest.restype = C.c_int
+    L.ksim_last_form.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.ksim_shard_setup.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
     L.ksim_shard_export.argtypes = [C.c_void_p, C.c_void_p]
     L.ksim_shard_connect.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

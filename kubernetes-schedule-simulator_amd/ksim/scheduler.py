@@ -445,6 +445,25 @@ class GenericScheduler:
         self.h.call("ksim_read_volumes", abi.vptr(slots), abi.vptr(cnt))
         return slots, cnt
 
+    def append_pods(self, pods, ports=None, scalars=None):
+        """Append descriptors (abi.POD_DTYPE) to the loaded queue (ksim_append_pods): their port /
+        scalar offsets index the `ports` / `scalars` arrays passed with them, and their classes must
+        be in the loaded class tables.  schedule(first, count) then accepts the new range."""
+        pods = np.ascontiguousarray(pods, abi.POD_DTYPE)
+        ports = np.zeros(0, np.uint64) if ports is None else np.ascontiguousarray(ports, np.uint64)
+        scalars = np.zeros(0, abi.SCALAR_DTYPE) if scalars is None else np.ascontiguousarray(scalars, abi.SCALAR_DTYPE)
+        self.h.call("ksim_append_pods", abi.vptr(pods), len(pods), abi.vptr(ports), len(ports), abi.vptr(scalars),
+                    len(scalars))
+        self._pods = np.concatenate([self._pods, pods])
+
+    @property
+    def last_form(self):
+        """ksim_last_form: abi.FORM_* bits of the last schedule call's dominant kernel, its rows per
+        row thread in bits 8-15; 0 for every kernel but the specialised resource-only one."""
+        v = C.c_int32()
+        self.h.call("ksim_last_form", C.byref(v))
+        return v.value
+
     def schedule(self, first=0, count=None):
         """Schedule + assume pods [first, first+count) in order.
         Returns (node index per pod (-1 = FitError), reason histograms or None, stats)."""

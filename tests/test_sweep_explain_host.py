@@ -50,7 +50,7 @@ def test_library_exports_the_entry_beside_an_unchanged_abi():
     L = abi.lib()
     assert hasattr(L, "ksim_sweep_explain")
     assert L.ksim_abi_version() == abi.ABI_VERSION == 7
-    assert len(abi.EXPORTS) == len(set(abi.EXPORTS)) == 32
+    assert len(abi.EXPORTS) == len(set(abi.EXPORTS)) == 33
     assert "ksim_sweep_explain" not in abi.EXPORTS
     assert "ksim_sweep_explain" not in open(os.path.join(INCLUDE, "ksim.h")).read()
     assert len(L.ksim_sweep_explain.argtypes) == 11

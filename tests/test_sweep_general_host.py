@@ -51,7 +51,7 @@ def test_abi_is_unchanged():
     assert L.ksim_abi_version() == abi.ABI_VERSION == 7
     assert "ksim_sweep" in abi.EXPORTS and "ksim_sweep_nodes" in abi.EXPORTS
     assert not any("general" in name for name in abi.EXPORTS)
-    assert len(abi.EXPORTS) == len(set(abi.EXPORTS)) == 32
+    assert len(abi.EXPORTS) == len(set(abi.EXPORTS)) == 33
     for name in abi.EXPORTS:
         assert hasattr(L, name), name
 

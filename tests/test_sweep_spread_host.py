@@ -44,7 +44,7 @@ def test_headers_name_what_is_swept_and_what_is_refused():
 def test_abi_is_unchanged():
     L = abi.lib()
     assert L.ksim_abi_version() == abi.ABI_VERSION == 7
-    assert len(abi.EXPORTS) == len(set(abi.EXPORTS)) == 32
+    assert len(abi.EXPORTS) == len(set(abi.EXPORTS)) == 33
     assert not any("spread" in name for name in abi.EXPORTS)
 
 
