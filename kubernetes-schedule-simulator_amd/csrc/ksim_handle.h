@@ -1,6 +1,7 @@
 // ksim_handle.h — private host-side state of a ksim_handle, shared by the runtime
-// translation units (ksim_runtime.cpp: load / schedule / sweep / shard; ksim_cache.cpp: the
-// per-pod drop-in entry points and the scheduler-cache event mirror).  Not part of the C-ABI.
+// translation units (ksim_runtime.cpp: load / schedule / shard; ksim_sweep_rt.cpp: the scenario
+// sweeps; ksim_cache.cpp: the per-pod drop-in entry points and the scheduler-cache event mirror).
+// Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,16 +45,10 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
                                         const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgsWhy* args,
                                         int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
                                         hipEvent_t ev1, hipStream_t st);
-extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsWhy* args,
-                                                int32_t n_scen, const uint32_t* absent, int32_t absent_words,
-                                                int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
-extern "C" hipError_t ksim_sweep_drain_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                              int32_t n_scen, const uint32_t* absent, int32_t absent_words,
-                                              int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
-extern "C" hipError_t ksim_sweep_spread_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                               const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
-                                               int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                                               hipStream_t st);
+extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
+                                                const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
+                                                int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
+                                                hipStream_t st);
 extern "C" int ksim_pfast_config(int64_t n, int max_grid, int stream, int* grid, int* lds_rows);
 extern "C" hipError_t ksim_pstream_prepare(const KsimCtx* c, double* mirror, hipStream_t s);
 extern "C" size_t ksim_pfast_granule_bytes(void);
@@ -380,7 +375,8 @@ static int dev_grow(ksim_handle* h, T** p, size_t keep, size_t new_cap) {
   return KSIM_OK;
 }
 
-// ---- runtime internals shared across translation units (ksim_runtime.cpp) ----
+// ---- runtime internals shared across translation units (defined in ksim_runtime.cpp; read by
+// ksim_sweep_rt.cpp and ksim_cache.cpp) ----
 // Append pods to the queue (first call: the initial load).  Validates, grows the device
 // arrays, extends the per-pod host bookkeeping (fast-kernel eligibility, tree classes).
 int ksim_rt_append(ksim_handle* h, const ksim_pod* pods, int64_t n_pods, const uint64_t* ports, int64_t n_ports,

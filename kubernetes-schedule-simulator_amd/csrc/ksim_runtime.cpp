@@ -1,14 +1,11 @@
-// ksim_runtime.cpp — host side of libksim.so: the C-ABI declared in include/ksim.h,
-// include/ksim_whatif.h and include/ksim_drain.h.
+// ksim_runtime.cpp — host side of libksim.so: the C-ABI declared in include/ksim.h, but for the
+// scenario sweeps (ksim_sweep_rt.cpp) and the per-pod entry points (ksim_cache.cpp).
 //
 // Owns the device-resident node table (SoA columns in HBM), the pod-class tables, the
 // pod queue and the run state, and drives the scan kernels on one HIP stream per handle.
 // No torch types cross this boundary; every entry point calls hipSetDevice (cgo calls may
 // land on any OS thread) and returns a KSIM_* status.
 #include "ksim_handle.h"
-
-#include "../../include/ksim_drain.h"
-#include "../../include/ksim_whatif.h"
 
 namespace {
 thread_local std::string g_err;
@@ -1478,682 +1475,6 @@ int ksim_evaluate(ksim_handle* h, int64_t pod, uint8_t* out_fit, uint32_t* out_r
   // release the scratch buffers again
   for (void* p : {(void*)f, (void*)r, (void*)s, (void*)rcl}) dev_free(h, p);
   return KSIM_OK;
-}
-
-// per-scenario pods bound (ksim_sweep_nodes out_scheduled)
-static void sweep_scheduled(const int32_t* out_node, int32_t n_scen, int64_t count, int32_t* out_scheduled) {
-  if (!out_scheduled) return;
-  for (int32_t s = 0; s < n_scen; ++s) {
-    int32_t b = 0;
-    for (int64_t k = 0; k < count; ++k) b += out_node[(size_t)s * count + k] >= 0;
-    out_scheduled[s] = b;
-  }
-}
-
-// ---- ksim_sweep_explain (include/ksim_whatif.h): the failed pods' records ----
-// failed pods of scenario s's prefix queue (ksim_sweep_drain; none without one)
-static int64_t pre_failed(const ksim_sweep_requeue* rq, int32_t s) {
-  int64_t nf = 0;
-  for (int64_t k = rq ? rq->off[s] : 0; rq && k < rq->off[s + 1]; ++k) nf += rq->out_node[k] < 0;
-  return nf;
-}
-// Records a scenario keeps on the device: none without a record array, and never more than the
-// range has pods.
-static int32_t why_cap(const ksim_sweep_failures* fail, int64_t count) {
-  return fail && fail->cap > 0 ? (int32_t)std::min<int64_t>(fail->cap, count) : 0;
-}
-// device bytes of one scenario's records: [cap] pod indices + [cap][KSIM_NREASONS] histograms
-static size_t why_bytes(int32_t cap) { return (size_t)cap * (1 + KSIM_NREASONS) * 4; }
-
-// A chunk's records ([nsc][cap] pods, [nsc][cap][KSIM_NREASONS] histograms on the device) into the
-// caller's arrays at the chunk's scenario offset s0: per scenario the first min(failed, cap), the
-// words past them left unwritten.  out_node: the chunk's placements, already on the host.
-// rq (ksim_sweep_drain): the scenarios' prefix answers, already on the host, count as well.
-static int why_copy_out(ksim_handle* h, const ksim_sweep_failures* fail, int32_t cap, int32_t s0, int32_t nsc,
-                        int64_t count, const int32_t* out_node, const int32_t* dpod, const int32_t* dhist,
-                        const ksim_sweep_requeue* rq = nullptr) {
-  if (!cap) return KSIM_OK;
-  std::vector<int32_t> kept((size_t)nsc);
-  size_t total = 0;
-  for (int32_t s = 0; s < nsc; ++s) {
-    int64_t nf = pre_failed(rq, s0 + s);
-    for (int64_t k = 0; k < count; ++k) nf += out_node[(size_t)s * count + k] < 0;
-    kept[s] = (int32_t)std::min<int64_t>(nf, cap);
-    total += (size_t)kept[s];
-  }
-  if (!total) return KSIM_OK;
-  const size_t ucap = (size_t)fail->cap;  // the caller's stride
-  // few kept records in a large chunk: one copy per scenario; else the chunk's arrays in one go
-  const bool whole = total * 4 >= (size_t)nsc * cap || (size_t)nsc * why_bytes(cap) <= ((size_t)8 << 20);
-  std::vector<int32_t> hp, hh;
-  if (whole) {
-    hp.resize((size_t)nsc * cap);
-    hh.resize((size_t)nsc * cap * KSIM_NREASONS);
-    HIPCHK(h, hipMemcpy(hp.data(), dpod, hp.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(hh.data(), dhist, hh.size() * 4, hipMemcpyDeviceToHost));
-  }
-  for (int32_t s = 0; s < nsc; ++s) {
-    const size_t k = (size_t)kept[s];
-    if (!k) continue;
-    int32_t* up = fail->pod + (size_t)(s0 + s) * ucap;
-    int32_t* uh = fail->hist + (size_t)(s0 + s) * ucap * KSIM_NREASONS;
-    if (whole) {
-      memcpy(up, hp.data() + (size_t)s * cap, k * 4);
-      memcpy(uh, hh.data() + (size_t)s * cap * KSIM_NREASONS, k * KSIM_NREASONS * 4);
-    } else {
-      HIPCHK(h, hipMemcpy(up, dpod + (size_t)s * cap, k * 4, hipMemcpyDeviceToHost));
-      HIPCHK(h, hipMemcpy(uh, dhist + (size_t)s * cap * KSIM_NREASONS, k * KSIM_NREASONS * 4, hipMemcpyDeviceToHost));
-    }
-  }
-  return KSIM_OK;
-}
-
-// count[s] = failed pods, listed[s] = n - |absent set of s| (bits at or above n ignored)
-static void why_counts(const ksim_sweep_failures* fail, const uint32_t* absent, int64_t n, int32_t n_scen, int64_t count,
-                       const int32_t* out_node, const ksim_sweep_requeue* rq = nullptr) {
-  if (!fail) return;
-  const int32_t aw = (int32_t)((n + 31) / 32);
-  for (int32_t s = 0; s < n_scen; ++s) {
-    if (fail->count) {
-      int32_t nf = (int32_t)pre_failed(rq, s);
-      for (int64_t k = 0; k < count; ++k) nf += out_node[(size_t)s * count + k] < 0;
-      fail->count[s] = nf;
-    }
-    if (fail->listed) {
-      int64_t gone = 0;
-      for (int32_t w = 0; absent && w < aw; ++w) {
-        uint32_t m = absent[(size_t)s * aw + w];
-        if (w == aw - 1 && (n & 31)) m &= (1u << (n & 31)) - 1u;
-        gone += __builtin_popcount(m);
-      }
-      fail->listed[s] = (int32_t)(n - gone);
-    }
-  }
-}
-
-// The general form of the sweep (ksim_sweep_general_kernel): a range with a pod that is not
-// resource-only.  Arguments as sweep_impl, which has checked them.
-// rq (ksim_sweep_drain, which has checked it): every scenario's prefix queue, scheduled before the
-// range; count may then be 0 and weights are NULL.
-static int sweep_general(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
-                         int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                         const ksim_sweep_failures* fail, ksim_stats* st, const ksim_sweep_requeue* rq = nullptr,
-                         int32_t* out_rehosted = nullptr) {
-  KsimCtx& c = h->ctx;
-  const int64_t n = c.n;
-  const size_t T = rq ? (size_t)rq->off[n_scen] : 0;  // prefix pods of all scenarios
-  int64_t mmax = 0;
-  for (int32_t s = 0; rq && s < n_scen; ++s) mmax = std::max(mmax, rq->off[s + 1] - rq->off[s]);
-  const int32_t wcap = why_cap(fail, mmax + count);  // over the longest scenario queue
-  if (h->shard.world > 1) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a node-sharded handle sweeps resource-only pods only", who);
-  if (n > KSIM_SWEEP_GENERAL_MAX_NODES)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout of pods that are not "
-                                       "resource-only", who, (long long)n, KSIM_SWEEP_GENERAL_MAX_NODES);
-  // A pod with affinity state is swept when that state is SelectorSpread's alone (the SPR
-  // instantiations): no affinity / anti-affinity term of any pod class, no term carried by a running
-  // pod, no auxiliary or lender tables, and the zones within the kernel's LDS words.
-  char spr_no[96] = "";
-  if (h->have_aff) {
-    if (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car)
-      snprintf(spr_no, sizeof spr_no, " (the tables hold inter-pod affinity terms: only SelectorSpread state is swept)");
-    else if (ksim_rt_launch_tables(h))
-      snprintf(spr_no, sizeof spr_no, " (auxiliary spreading priority or lender tables are loaded)");
-    else if (h->aff_n_zone > KSIM_SWEEP_SPREAD_MAX_ZONES)
-      snprintf(spr_no, sizeof spr_no, " (%d zones exceed the %d zones of a swept SelectorSpread queue)", h->aff_n_zone,
-               KSIM_SWEEP_SPREAD_MAX_ZONES);
-  }
-  bool spr = ksim_rt_aff_count(h, first, count) > 0;
-  if (spr && spr_no[0])
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state%s", who, spr_no);
-  for (int64_t q = first; q < first + count; ++q)
-    if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: pod %lld mounts volumes", who, (long long)q);
-  if (ksim_rt_launch_tables(h))
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: an auxiliary spreading priority or CheckServiceAffinity's lender table is "
-                                       "loaded", who);
-  if (ksim_rt_range_wide(h, first, count))
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod class in the range has more than %d reduce classes", who,
-                KSIM_MAX_RCLASS);
-  if (T) {  // the same refusals for the distinct prefix pods
-    std::vector<int64_t> idx(rq->pod, rq->pod + T);
-    std::sort(idx.begin(), idx.end());
-    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
-    for (int64_t q : idx) {
-      if (ksim_rt_aff_count(h, q, 1)) {
-        if (spr_no[0])
-          return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld carries inter-pod affinity or spread state%s", who,
-                      (long long)q, spr_no);
-        spr = true;
-      }
-      if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld mounts volumes", who, (long long)q);
-      if (ksim_rt_range_wide(h, q, 1))
-        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the class of re-queued pod %lld has more than %d reduce classes", who,
-                    (long long)q, KSIM_MAX_RCLASS);
-    }
-  }
-  if (weights && (c.w[KSIM_W_TAINT_TOLERATION] || c.w[KSIM_W_NODE_AFFINITY] || c.use_na))
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over pods that are not resource-only would drop the "
-                                       "handle's reduce priorities or NodePreferAvoidPods addend (weights = NULL sweeps "
-                                       "under the whole configured policy)", who);
-  // the spread weight a spread pod's packed score carries beside the map weights
-  const int64_t wspr = (spr && !c.no_prio) ? c.w[KSIM_W_SELECTOR_SPREAD] : 0;
-  if (weights && wspr)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over a SelectorSpread queue would drop the handle's "
-                                       "spread priority (weights = NULL sweeps under the whole configured policy)", who);
-  std::vector<int64_t> w3(weights ? (size_t)n_scen * 3 : 0);
-  for (int32_t sidx = 0; sidx < (weights ? n_scen : 1); ++sidx) {
-    const int64_t* w = weights ? weights + (size_t)sidx * KSIM_NW : c.w;
-    if (weights && (w[KSIM_W_TAINT_TOLERATION] || w[KSIM_W_NODE_AFFINITY]))
-      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: reduce priorities are not swept", who, sidx);
-    // a packed evaluation holds the map score (and a spread pod's spread score) in
-    // KSIM_SWEEP_GENERAL_SCORE_BITS bits: 10 x (LeastRequested + MostRequested + Balanced + spread weight)
-    const int64_t lim = ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10;
-    if (wspr < 0 || wspr >= lim) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
-    int64_t tot = wspr;
-    for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED}) {
-      if (w[k] < 0 || w[k] >= lim) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
-      tot += w[k];
-    }
-    if (tot >= lim)
-      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: map scores exceed %d bits", who, sidx,
-                  KSIM_SWEEP_GENERAL_SCORE_BITS);
-    if (weights) {
-      w3[3 * (size_t)sidx] = w[KSIM_W_LEAST_REQUESTED];
-      w3[3 * (size_t)sidx + 1] = w[KSIM_W_MOST_REQUESTED];
-      w3[3 * (size_t)sidx + 2] = w[KSIM_W_BALANCED];
-    }
-  }
-  // scratch: a chunk of C scenarios' copies of every column a commit writes, their contexts and
-  // outputs, every scenario's weights and the sweep's error word.  The chunk follows the other
-  // forms' rule: at most 24 GiB and at most half of the device memory free now, halved while the
-  // allocation fails; one chunk is one launch.
-  const size_t S = (size_t)n_scen, N = (size_t)n, P = (size_t)count;
-  const size_t NS = (size_t)c.n_scalar, NP = (size_t)c.port_slots;
-  const int32_t aw = (int32_t)((n + 31) / 32);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
-  const size_t b_w = weights ? al(S * 24) : 0;
-  // the prefix queues of the whole sweep (off, pod, out_pre): uploaded once, indexed by global scenario
-  const size_t b_rq = rq ? al((S + 1) * 8) + al(T * 8) + al(T * 4) : 0;
-  // a SelectorSpread queue: a scenario's copy of the counted pairs and its affinity descriptor
-  const size_t CL = spr ? (size_t)h->aff_cnt_len : 0;
-  const size_t spr_per = spr ? CL * 4 + sizeof(KsimAff) : 0;
-  auto need_of = [&](size_t C) {
-    return 6 * al(C * N * 8) + 3 * al(C * N * 4) + al(C * N * NS * 8) + al(C * N * NP * 8) + al(C * sizeof(KsimCtx)) + b_w +
-           al(C * P * 4) + al(C * 8) + al(4) + (MW ? al(C * MW) : 0) + (wcap ? al(C * wcap * 4) + al(C * why_bytes(wcap) - C * wcap * 4) : 0) +
-           b_rq + (spr ? al(C * CL * 4) + al(C * sizeof(KsimAff)) : 0);
-  };
-  size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
-  if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
-  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + MW + why_bytes(wcap) + spr_per;
-  budget = budget > b_rq ? budget - b_rq : 0;
-  int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
-  if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
-  if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
-    if (h->sw_scratch) {
-      for (auto& b : h->bufs)
-        if (b.p == h->sw_scratch) b.p = nullptr;
-      (void)hipFree(h->sw_scratch);
-      h->sw_scratch = nullptr;
-      h->sw_scratch_bytes = 0;
-    }
-    char* p = nullptr;
-    for (;;) {
-      const size_t need = need_of((size_t)chunk);
-      if (hipMalloc((void**)&p, need) == hipSuccess) {
-        h->bufs.push_back({p, need});
-        h->sw_scratch = p;
-        h->sw_scratch_bytes = need;
-        break;
-      }
-      (void)hipGetLastError();
-      if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "%s: no device memory for one scenario (%zu bytes)", who, need);
-      chunk = (chunk + 1) / 2;
-    }
-  }
-  const size_t C = (size_t)chunk;
-  char* q = (char*)h->sw_scratch;
-  auto take = [&](size_t b) { char* r = q; q += al(b); return r; };
-  SwgCols cols{};
-  cols.req_cpu = (int64_t*)take(C * N * 8); cols.req_mem = (int64_t*)take(C * N * 8);
-  cols.req_gpu = (int64_t*)take(C * N * 8); cols.req_eph = (int64_t*)take(C * N * 8);
-  cols.nz_cpu = (int64_t*)take(C * N * 8); cols.nz_mem = (int64_t*)take(C * N * 8);
-  cols.pod_count = (int32_t*)take(C * N * 4); cols.port_count = (int32_t*)take(C * N * 4);
-  cols.flags = (uint32_t*)take(C * N * 4);
-  cols.req_scalar = (int64_t*)take(C * N * NS * 8);
-  cols.ports = (uint64_t*)take(C * N * NP * 8);
-  SwgArgsPre a{};
-  a.n_pods = (int32_t)count;
-  a.first = first;
-  a.ctx = (KsimCtx*)take(C * sizeof(KsimCtx));
-  int64_t* dw = weights ? (int64_t*)take(S * 24) : nullptr;
-  a.w = dw;
-  a.out_node = (int32_t*)take(C * P * 4);
-  a.out_counter = (uint64_t*)take(C * 8);
-  int32_t* derr = (int32_t*)take(4);  // ksim_commit's port-slot overflow bit (the handle's word is not written)
-  uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
-  if (wcap) {  // the chunk's records of failed pods (ksim_sweep_explain)
-    a.why.cap = wcap;
-    a.why.pod = (int32_t*)take(C * wcap * 4);
-    a.why.hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
-  }
-  if (rq) {
-    int64_t* doff = (int64_t*)take((S + 1) * 8);
-    int64_t* dpod = (int64_t*)take(T * 8);
-    a.off = doff;
-    a.pod = dpod;
-    a.out_pre = (int32_t*)take(T * 4);
-    HIPCHK(h, hipMemcpyAsync(doff, rq->off, (S + 1) * 8, hipMemcpyHostToDevice, ksim_stream(h)));
-    if (T) HIPCHK(h, hipMemcpyAsync(dpod, rq->pod, T * 8, hipMemcpyHostToDevice, ksim_stream(h)));
-  }
-  SwgSpread sprd{};
-  if (spr) {  // every launch copies the handle's current counts: the handle's own are only read
-    sprd.base = h->aff_h;
-    sprd.cnt_len = (int64_t)CL;
-    sprd.cnt = (int32_t*)take(C * CL * 4);
-    sprd.aff = (KsimAff*)take(C * sizeof(KsimAff));
-  }
-  HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
-  if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
-  HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
-  float ms = 0.f;
-  for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
-    const int32_t nsc = std::min(chunk, n_scen - s0);
-    a.scen0 = s0;  // the chunk's first scenario: its row of the weights
-    if (absent)
-      HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
-    hipError_t e = spr  ? ksim_sweep_spread_launch(&c, &cols, &a, &sprd, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h))
-                   : rq ? ksim_sweep_drain_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h))
-                        : ksim_sweep_general_launch(&c, &cols, &a, nsc, dabs, aw, derr, h->ev0, h->ev1, ksim_stream(h));
-    if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
-    HIPCHK(h, hipEventSynchronize(h->ev1));
-    float c_ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
-    ms += c_ms;
-    if (P) HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
-    if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
-    if (rq && rq->off[s0 + nsc] > rq->off[s0])  // the chunk's prefix answers
-      HIPCHK(h, hipMemcpy(rq->out_node + rq->off[s0], a.out_pre + rq->off[s0],
-                          (size_t)(rq->off[s0 + nsc] - rq->off[s0]) * 4, hipMemcpyDeviceToHost));
-    if (int rcw = why_copy_out(h, fail, wcap, s0, nsc, count, P ? out_node + (size_t)s0 * P : nullptr, a.why.pod,
-                               a.why.hist, rq))
-      return rcw;
-  }
-  int32_t err = 0;
-  HIPCHK(h, hipMemcpy(&err, derr, 4, hipMemcpyDeviceToHost));
-  if (err)
-    return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's host-port slots overflowed in a scenario (load the node table with "
-                                    "more port slots)", who);
-  if (st) {
-    memset(st, 0, sizeof *st);
-    st->pods = (int64_t)(S * P + T);
-    int64_t b = 0;
-    for (size_t k = 0; k < S * P; ++k) b += out_node[k] >= 0;
-    for (size_t k = 0; k < T; ++k) b += rq->out_node[k] >= 0;
-    st->scheduled = b;
-    st->node_evals = (int64_t)(S * P + T) * n;
-    st->device_ms = ms;
-    st->kernel_ms = ms;
-    st->kernel_launches = (n_scen + chunk - 1) / chunk;
-    st->mode = KSIM_MODE_PERSISTENT;
-    st->blocks = chunk;
-  }
-  sweep_scheduled(out_node, n_scen, count, out_scheduled);
-  for (int32_t s = 0; out_rehosted && s < n_scen; ++s)
-    out_rehosted[s] = (int32_t)(rq->off[s + 1] - rq->off[s] - pre_failed(rq, s));
-  why_counts(fail, absent, n, n_scen, count, out_node, rq);
-  return KSIM_OK;
-}
-
-// ksim_sweep (absent = NULL, weights given), ksim_sweep_nodes and ksim_sweep_explain (fail).  absent: [n_scen][ceil(n / 32)]
-// words, a set bit = the node is not listed in that scenario; weights NULL = the handle's own.
-static int sweep_impl(ksim_handle* h, const char* who, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
-                      int64_t first, int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                      const ksim_sweep_failures* fail, ksim_stats* st) {
-  if (!h || !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
-  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
-  if (n_scen <= 0 || first < 0 || count <= 0 || first + count > h->n_pods || count > INT32_MAX)
-    return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
-  HIPCHK(h, hipSetDevice(h->device));
-  KsimCtx& c = h->ctx;
-  const int64_t n = c.n;
-  if (n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
-  // a pod that is not resource-only (ports, selectors, taints, nodeName, gpu / ephemeral / extended
-  // requests, more than one reduce class): the general form; else the forms below, as ever
-  if (h->fast_pre[first + count] - h->fast_pre[first] != count)
-    return sweep_general(h, who, weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st);
-  if (n > KSIM_SWEEP_MAX_NODES)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout", who, (long long)n,
-                KSIM_SWEEP_MAX_NODES);
-  std::vector<int32_t> w3((size_t)n_scen * 3);
-  for (int32_t sidx = 0; sidx < n_scen; ++sidx) {
-    // weights NULL: the handle's own map weights.  Its reduce and constant priorities are the same
-    // value on every node for the pods admitted above (fast_k: one reduce class) and stay out of
-    // the packed score, as in the fast persistent kernel.
-    const int64_t* w = weights ? weights + (size_t)sidx * KSIM_NW : c.w;
-    if (weights && (w[KSIM_W_TAINT_TOLERATION] || w[KSIM_W_NODE_AFFINITY]))
-      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: reduce priorities are not swept", who, sidx);
-    int64_t tot = 0;
-    for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED}) {
-      if (w[k] < 0 || w[k] > 6553) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range", who, sidx);
-      tot += w[k];
-    }
-    if (tot * 10 >= 0xFFFF) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: scores exceed 16 bits", who, sidx);
-    w3[3 * sidx] = (int32_t)w[KSIM_W_LEAST_REQUESTED];
-    w3[3 * sidx + 1] = (int32_t)w[KSIM_W_MOST_REQUESTED];
-    w3[3 * sidx + 2] = (int32_t)w[KSIM_W_BALANCED];
-  }
-  // float64 exactness: capacities below 2^48 (they never grow), and the requested quantities +
-  // count x the largest pod quantity stay below 2^48
-  {
-    int64_t qmax = 0, nmax = 0, amax = 0;
-    for (int64_t i = first; i < first + count; ++i) qmax = std::max(qmax, h->pod_qmax[i]);
-    std::vector<int64_t> col((size_t)n);
-    for (const int64_t* d : {c.alloc_cpu, c.alloc_mem, (const int64_t*)c.req_cpu, (const int64_t*)c.req_mem,
-                             (const int64_t*)c.nz_cpu, (const int64_t*)c.nz_mem}) {
-      HIPCHK(h, hipMemcpy(col.data(), d, (size_t)n * 8, hipMemcpyDeviceToHost));
-      int64_t& mx = (d == c.alloc_cpu || d == c.alloc_mem) ? amax : nmax;
-      for (int64_t v : col) mx = std::max(mx, v < 0 ? INT64_MAX / 2 : v);
-    }
-    const int64_t lim = (int64_t)1 << 48;
-    if (amax >= lim || nmax >= lim || qmax >= lim || count > lim / std::max<int64_t>(qmax, 1) || nmax + count * qmax >= lim)
-      return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: quantities may leave the exact float64 range (2^48)", who);
-  }
-  int rc;
-  const int32_t aw = (int32_t)((n + 31) / 32);  // node-set words per scenario
-  const int32_t wcap = why_cap(fail, count);    // records of failed pods kept per scenario (ksim_sweep_explain)
-  // Tree form (ksim_tree.hip): one tree-mode wave per scenario, scenarios spread over the CUs.
-  if (!getenv("KSIM_SWEEP_SCAN") && h->n_tcls > 0 && n < ((int64_t)1 << 24) && !h->pfast_off) {
-    KsimTreeGeo g{};
-    // a small LDS plan: several scenarios' waves per CU hide each other's memory latency
-    const char* lb = getenv("KSIM_SWEEP_LDS");
-    if (ksim_tree_plan(n, h->n_tcls, lb ? atoll(lb) : 24 * 1024, 0, &g) || ksim_tree_plan(n, h->n_tcls, 0, 0, &g)) {
-      if (!h->t_y && (rc = dev_alloc(h, &h->t_y, (size_t)2 * n))) return rc;
-      auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-      const size_t N = (size_t)n, P = (size_t)count, K = (size_t)g.K;
-      const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
-      const size_t per = al(4 * N * 8) + al(N * 4) + al(K * g.st[0] * 4) + al(g.level_entries * 8) + al(K * 4) + al(8) +
-                         al(P * 4) + al(sizeof(kf64::EvCfg)) + (MW ? al(MW) : 0) + al(why_bytes(wcap));
-      // scratch budget: at most 24 GiB (all 4,096 C5 scenarios, ~3.7 MB each, in one launch) and
-      // at most half of the device memory free now (a shared or smaller device gets smaller chunks)
-      size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
-      if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
-      int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)n_scen, budget / per));
-      if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
-      auto need_of = [&](size_t C) {
-        return C * (al(4 * N * 8) + al(N * 4)) + al(C * K * g.st[0] * 4) + al(C * g.level_entries * 8) + al(C * K * 4) +
-               al(C * 8) + al(C * P * 4) + al(C * sizeof(kf64::EvCfg)) + (MW ? al(C * MW) : 0) +
-               (wcap ? al(C * wcap * 4) + al(C * wcap * KSIM_NREASONS * 4) : 0) + 4096;
-      };
-      if (h->swt_bytes < need_of((size_t)chunk)) {
-        if (h->swt_scratch) {
-          for (auto& b : h->bufs)
-            if (b.p == h->swt_scratch) b.p = nullptr;
-          (void)hipFree(h->swt_scratch);
-          h->swt_scratch = nullptr;
-          h->swt_bytes = 0;
-        }
-        // an allocation that fails halves the scenario chunk until one fits (one scenario at least)
-        char* p = nullptr;
-        for (;;) {
-          const size_t need = need_of((size_t)chunk);
-          if (hipMalloc((void**)&p, need) == hipSuccess) {
-            h->bufs.push_back({p, need});
-            h->swt_scratch = p;
-            h->swt_bytes = need;
-            break;
-          }
-          (void)hipGetLastError();
-          if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "%s: no device memory for one scenario (%zu bytes)", who, need);
-          chunk = (chunk + 1) / 2;
-        }
-      }
-      const size_t C = (size_t)chunk;
-      char* q = (char*)h->swt_scratch;
-      auto take = [&](size_t b) { char* r = q; q += al(b); return r; };
-      KsimTreeSweep sw{};
-      sw.count_pods = count;
-      sw.rc = (int64_t*)take(C * N * 8); sw.rm = (int64_t*)take(C * N * 8);
-      sw.zc = (int64_t*)take(C * N * 8); sw.zm = (int64_t*)take(C * N * 8);
-      sw.count = (int32_t*)take(C * N * 4);
-      int32_t* leaves = (int32_t*)take(C * K * g.st[0] * 4);
-      uint64_t* levels = (uint64_t*)take(C * g.level_entries * 8);
-      int32_t* fitc = (int32_t*)take(C * K * 4);
-      sw.counter = (uint64_t*)take(C * 8);
-      sw.out_node = (int32_t*)take(C * P * 4);
-      kf64::EvCfg* dcfg = (kf64::EvCfg*)take(C * sizeof(kf64::EvCfg));
-      sw.cfg = dcfg;
-      uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
-      if (wcap) {  // the chunk's records of failed pods
-        sw.why_cap = wcap;
-        sw.why_pod = (int32_t*)take(C * wcap * 4);
-        sw.why_hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
-      }
-      std::vector<kf64::EvCfg> cfgs((size_t)n_scen);
-      for (int32_t sidx = 0; sidx < n_scen; ++sidx)
-        cfgs[sidx] = kf64::make_evcfg(c.preds, c.no_prio != 0, w3[3 * sidx], w3[3 * sidx + 1], w3[3 * sidx + 2]);
-      const int64_t save_first = c.first, save_end = c.end;
-      c.first = first;
-      c.end = first + count;
-      float kms = 0.f, dms = 0.f;
-      int32_t err0 = 0;
-      HIPCHK(h, hipMemcpy(&err0, c.err, 4, hipMemcpyDeviceToHost));
-      for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
-        sw.nsc = std::min(chunk, n_scen - s0);
-        HIPCHK(h, hipMemcpyAsync(dcfg, cfgs.data() + s0, sw.nsc * sizeof(kf64::EvCfg), hipMemcpyHostToDevice, ksim_stream(h)));
-        HIPCHK(h, hipEventRecord(h->ev0, ksim_stream(h)));
-        if (absent)
-          HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)sw.nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
-        hipError_t e = ksim_tree_sweep_init(&c, &sw, ksim_stream(h));
-        if (e == hipSuccess && absent) e = ksim_tree_sweep_absent(&c, &sw, dabs, aw, ksim_stream(h));
-        if (e == hipSuccess)
-          e = absent ? ksim_tree_build_absent(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h))
-                     : ksim_tree_build(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h));
-        if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "tree sweep build: %s", hipGetErrorString(e));
-        HIPCHK(h, hipEventRecord(h->ev1, ksim_stream(h)));
-        e = ksim_tree_launch(&c, &g, h->tclass, h->tcls, leaves, levels, fitc, h->t_y, &sw, ksim_stream(h));
-        if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "tree sweep launch: %s", hipGetErrorString(e));
-        hipEvent_t ev2 = nullptr;
-        HIPCHK(h, hipEventCreate(&ev2));
-        HIPCHK(h, hipEventRecord(ev2, ksim_stream(h)));
-        HIPCHK(h, hipEventSynchronize(ev2));
-        float b_ms = 0.f, r_ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&b_ms, h->ev0, h->ev1));
-        HIPCHK(h, hipEventElapsedTime(&r_ms, h->ev1, ev2));
-        (void)hipEventDestroy(ev2);
-        kms += r_ms;
-        dms += b_ms + r_ms;
-        HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, sw.out_node, (size_t)sw.nsc * P * 4, hipMemcpyDeviceToHost));
-        if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, sw.counter, (size_t)sw.nsc * 8, hipMemcpyDeviceToHost));
-        if (int rcw = why_copy_out(h, fail, wcap, s0, sw.nsc, count, out_node + (size_t)s0 * P, sw.why_pod, sw.why_hist)) {
-          c.first = save_first;
-          c.end = save_end;
-          return rcw;
-        }
-      }
-      c.first = save_first;
-      c.end = save_end;
-      int32_t err = 0;
-      HIPCHK(h, hipMemcpy(&err, c.err, 4, hipMemcpyDeviceToHost));
-      if (err != err0) {
-        HIPCHK(h, hipMemcpy(c.err, &err0, 4, hipMemcpyHostToDevice));
-        return ksim_fail(h, KSIM_E_DEVICE, "tree sweep: device consistency error 0x%x", err & ~err0);
-      }
-      if (st) {
-        memset(st, 0, sizeof *st);
-        st->pods = (int64_t)(n_scen * P);
-        int64_t b = 0;
-        for (size_t k = 0; k < (size_t)n_scen * P; ++k) b += out_node[k] >= 0;
-        st->scheduled = b;
-        st->node_evals = (int64_t)(n_scen * P) * n;
-        st->device_ms = dms;
-        st->kernel_ms = kms;
-        st->kernel_launches = (n_scen + chunk - 1) / chunk;
-        st->mode = KSIM_MODE_TREE;
-        st->blocks = chunk;
-      }
-      sweep_scheduled(out_node, n_scen, count, out_scheduled);
-      why_counts(fail, absent, n, n_scen, count, out_node);
-      return KSIM_OK;
-    }
-  }
-  if (!h->sw_dac) {
-    if ((rc = dev_alloc(h, &h->sw_dac, n)) || (rc = dev_alloc(h, &h->sw_dam, n)) || (rc = dev_alloc(h, &h->sw_yc, n)) ||
-        (rc = dev_alloc(h, &h->sw_ym, n)))
-      return rc;
-    hipError_t e = ksim_sweep_prepare(c.alloc_cpu, c.alloc_mem, n, h->sw_dac, h->sw_dam, h->sw_yc, h->sw_ym, ksim_stream(h));
-    if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep prepare: %s", hipGetErrorString(e));
-  }
-  // scratch: [C][n] x (4 float64 + int32) and outputs for a chunk of C scenarios, the pods and every
-  // scenario's weights.  The chunk follows the tree form's rule: at most 24 GiB and at most half
-  // of the device memory free now, halved while the allocation fails; one chunk is one launch.
-  const size_t S = (size_t)n_scen, N = (size_t)n, P = (size_t)count;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t MW = absent ? (size_t)aw * 4 : 0;  // a scenario's node-set words
-  const size_t b_pod = al(P * sizeof(kf64::FPod)), b_w = al(S * 12);
-  auto need_of = [&](size_t C) {
-    return 4 * al(C * N * 8) + al(C * N * 4) + b_pod + b_w + al(C * P * 4) + al(C * 8) + (MW ? al(C * MW) : 0) +
-           (wcap ? al(C * wcap * 4) + al(C * wcap * KSIM_NREASONS * 4) : 0);
-  };
-  size_t budget = (size_t)24 << 30, mfree = 0, mtotal = 0;
-  if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree / 2 < budget) budget = mfree / 2;
-  const size_t per = N * 36 + P * 4 + 8 + MW + why_bytes(wcap);
-  int32_t chunk = (int32_t)std::max<size_t>(1, std::min<size_t>(S, budget / per));
-  if (const char* ch = getenv("KSIM_SWEEP_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(ch)));  // tests
-  if (h->sw_scratch_bytes < need_of((size_t)chunk)) {
-    if (h->sw_scratch) {
-      for (auto& b : h->bufs)
-        if (b.p == h->sw_scratch) b.p = nullptr;
-      (void)hipFree(h->sw_scratch);
-      h->sw_scratch = nullptr;
-      h->sw_scratch_bytes = 0;
-    }
-    char* p = nullptr;
-    for (;;) {
-      const size_t need = need_of((size_t)chunk);
-      if (hipMalloc((void**)&p, need) == hipSuccess) {
-        h->bufs.push_back({p, need});
-        h->sw_scratch = p;
-        h->sw_scratch_bytes = need;
-        break;
-      }
-      (void)hipGetLastError();
-      if (chunk == 1) return ksim_fail(h, KSIM_E_NOMEM, "%s: no device memory for one scenario (%zu bytes)", who, need);
-      chunk = (chunk + 1) / 2;
-    }
-  }
-  const size_t C = (size_t)chunk;
-  char* q = (char*)h->sw_scratch;
-  auto take = [&](size_t b) { char* r = q; q += al(b); return r; };
-  SwArgsWhy a{};
-  a.n = n; a.n_pods = (int32_t)count;
-  a.dac = h->sw_dac; a.dam = h->sw_dam; a.yc = h->sw_yc; a.ym = h->sw_ym;
-  a.allowed = c.allowed_pods; a.flags = c.flags;
-  a.rc = (double*)take(C * N * 8); a.rm = (double*)take(C * N * 8);
-  a.zc = (double*)take(C * N * 8); a.zm = (double*)take(C * N * 8);
-  a.count = (int32_t*)take(C * N * 4);
-  a.pods = (const kf64::FPod*)take(P * sizeof(kf64::FPod));
-  int32_t* dw = (int32_t*)take(S * 12);
-  a.w = dw;
-  a.out_node = (int32_t*)take(C * P * 4);
-  a.out_counter = (uint64_t*)take(C * 8);
-  uint32_t* dabs = absent ? (uint32_t*)take(C * MW) : nullptr;  // the chunk's slice of the node sets
-  if (wcap) {  // the chunk's records of failed pods
-    a.why.cap = wcap;
-    a.why.pod = (int32_t*)take(C * wcap * 4);
-    a.why.hist = (int32_t*)take(C * wcap * KSIM_NREASONS * 4);
-  }
-  a.preds = c.preds; a.no_prio = c.no_prio;
-  HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 12, hipMemcpyHostToDevice, ksim_stream(h)));
-  float ms = 0.f;
-  for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
-    const int32_t nsc = std::min(chunk, n_scen - s0);
-    a.scen0 = s0;  // the chunk's first scenario: its row of the weights
-    if (absent)
-      HIPCHK(h, hipMemcpyAsync(dabs, absent + (size_t)s0 * aw, (size_t)nsc * MW, hipMemcpyHostToDevice, ksim_stream(h)));
-    hipError_t e = ksim_sweep_launch(c.req_cpu, c.req_mem, c.nz_cpu, c.nz_mem, c.pod_count, c.pods + first,
-                                     (void*)a.pods, &a, nsc, dabs, aw, h->ev0, h->ev1, ksim_stream(h));
-    if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
-    HIPCHK(h, hipEventSynchronize(h->ev1));
-    float c_ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
-    ms += c_ms;
-    HIPCHK(h, hipMemcpy(out_node + (size_t)s0 * P, a.out_node, (size_t)nsc * P * 4, hipMemcpyDeviceToHost));
-    if (out_counters) HIPCHK(h, hipMemcpy(out_counters + s0, a.out_counter, (size_t)nsc * 8, hipMemcpyDeviceToHost));
-    if (int rcw = why_copy_out(h, fail, wcap, s0, nsc, count, out_node + (size_t)s0 * P, a.why.pod, a.why.hist)) return rcw;
-  }
-  if (st) {
-    memset(st, 0, sizeof *st);
-    st->pods = (int64_t)(S * P);
-    int64_t b = 0;
-    for (size_t k = 0; k < S * P; ++k) b += out_node[k] >= 0;
-    st->scheduled = b;
-    st->node_evals = (int64_t)(S * P) * n;
-    st->device_ms = ms;
-    st->kernel_ms = ms;
-    st->kernel_launches = (n_scen + chunk - 1) / chunk;
-    st->mode = KSIM_MODE_PERSISTENT;
-    st->blocks = chunk;
-  }
-  sweep_scheduled(out_node, n_scen, count, out_scheduled);
-  why_counts(fail, absent, n, n_scen, count, out_node);
-  return KSIM_OK;
-}
-
-int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count, int32_t* out_node,
-               uint64_t* out_counters, ksim_stats* st) {
-  if (!weights) return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep: null argument");
-  return sweep_impl(h, "ksim_sweep", weights, nullptr, n_scen, first, count, out_node, out_counters, nullptr, nullptr, st);
-}
-
-int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
-                     int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled, ksim_stats* st) {
-  return sweep_impl(h, "ksim_sweep_nodes", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
-                    nullptr, st);
-}
-
-int ksim_sweep_drain(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_requeue* rq, int64_t first,
-                     int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                     int32_t* out_rehosted, const ksim_sweep_failures* fail, ksim_stats* st) {
-  const char* who = "ksim_sweep_drain";
-  // what needs no device, before the handle is touched
-  if (fail && (fail->cap < 0 || (fail->cap > 0 && (!fail->pod || !fail->hist))))
-    return ksim_fail(h, KSIM_E_INVAL, "%s: a negative record cap, or a cap without record arrays", who);
-  if (n_scen <= 0 || first < 0 || count < 0) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
-  if (!rq || !rq->off) return ksim_fail(h, KSIM_E_INVAL, "%s: null re-queue lists", who);
-  if (rq->off[0] != 0) return ksim_fail(h, KSIM_E_INVAL, "%s: off[0] must be 0", who);
-  for (int32_t s = 0; s < n_scen; ++s) {
-    if (rq->off[s + 1] < rq->off[s]) return ksim_fail(h, KSIM_E_INVAL, "%s: off decreases at scenario %d", who, s);
-    if (rq->off[s + 1] - rq->off[s] > (int64_t)INT32_MAX - count)
-      return ksim_fail(h, KSIM_E_INVAL, "%s: the queue of scenario %d exceeds INT32_MAX pods", who, s);
-  }
-  const int64_t T = rq->off[n_scen];
-  if (T > 0 && (!rq->pod || !rq->out_node))
-    return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pods without a pod or out_node array", who);
-  if (T == 0 && count == 0) return ksim_fail(h, KSIM_E_INVAL, "%s: neither re-queued pods nor a pod range", who);
-  if (count > 0 && !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
-  if (!h) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
-  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
-  if (first + count > h->n_pods) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
-  for (int64_t k = 0; k < T; ++k)
-    if (rq->pod[k] < 0 || rq->pod[k] >= h->n_pods)
-      return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pod index %lld outside the loaded queue of %lld pods", who,
-                  (long long)rq->pod[k], (long long)h->n_pods);
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
-  return sweep_general(h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
-                       out_rehosted);
-}
-
-int ksim_sweep_explain(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
-                       int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
-                       const ksim_sweep_failures* fail, ksim_stats* st) {
-  if (fail && (fail->cap < 0 || (fail->cap > 0 && (!fail->pod || !fail->hist))))
-    return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep_explain: a negative record cap, or a cap without record arrays");
-  return sweep_impl(h, "ksim_sweep_explain", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
-                    fail, st);
 }
 
 int ksim_shard_setup(ksim_handle* h, int32_t rank, int32_t world, int64_t node_base) {

@@ -665,6 +665,15 @@ __global__ void ksim_sweep_pods_kernel(const ksim_pod* pods, int64_t count, FPod
   if (i < count) out[i] = load_fpod(pods[i]);
 }
 
+// A run-time flag as a compile-time one: f(std::true_type) or f(std::false_type), so that a launcher
+// names its kernel once, <decltype(ABS)::value, ...>.  A kernel takes the argument struct of its
+// instantiation by value: the launchers pass the fullest one and the call keeps the base part.
+template <class F>
+static void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 extern "C" size_t ksim_sweep_fpod_bytes(void) { return sizeof(FPod); }
 
 extern "C" hipError_t ksim_sweep_prepare(const int64_t* ac, const int64_t* am, int64_t n, double* dac, double* dam,
@@ -691,14 +700,12 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
   if (ev0) (void)hipEventRecord(ev0, st);
   const size_t lds = (size_t)n * sizeof(uint16_t);
   const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
-  if (absent && why)
-    hipLaunchKernelGGL((ksim_sweep_kernel<true, true>), dim3((unsigned)n_scen), dim3(SB), lds, st, *args);
-  else if (absent)
-    hipLaunchKernelGGL((ksim_sweep_kernel<true, false>), dim3((unsigned)n_scen), dim3(SB), lds, st, (const SwArgs&)*args);
-  else if (why)
-    hipLaunchKernelGGL((ksim_sweep_kernel<false, true>), dim3((unsigned)n_scen), dim3(SB), lds, st, *args);
-  else
-    hipLaunchKernelGGL((ksim_sweep_kernel<false, false>), dim3((unsigned)n_scen), dim3(SB), lds, st, (const SwArgs&)*args);
+  with_flag(absent != nullptr, [&](auto ABS) {
+    with_flag(why, [&](auto WHY) {
+      hipLaunchKernelGGL((ksim_sweep_kernel<decltype(ABS)::value, decltype(WHY)::value>), dim3((unsigned)n_scen),
+                         dim3(SB), lds, st, *args);
+    });
+  });
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;
@@ -706,11 +713,14 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
 
 // The general form: hc the handle's context, cols the chunk's scenario columns, err the sweep's own
 // error word (ksim_commit's port-slot overflow bit; the handle's word is never written).
-// args->off set: the PRE instantiations (ksim_sweep_drain).
-// spr set: the SPR instantiations (a SelectorSpread queue).
-static hipError_t swg_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args, int32_t n_scen,
-                             const uint32_t* absent, int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                             hipStream_t st, const SwgSpread* spr = nullptr) {
+// args->off set: the PRE instantiations (ksim_sweep_drain); off / pod / out_pre are the whole
+// sweep's, indexed by args->scen0 + the chunk's scenario.
+// spr set: the SPR instantiations (a SelectorSpread queue): the handle's affinity descriptor and the
+// chunk's count copies and per-scenario descriptors.
+extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
+                                                const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
+                                                int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
+                                                hipStream_t st) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
   if (spr) {
     const int64_t ct = spr->cnt_len * (int64_t)n_scen, thr = ct > n_scen ? ct : (int64_t)n_scen;
@@ -738,60 +748,25 @@ static hipError_t swg_launch(const KsimCtx* hc, const SwgCols* cols, const SwgAr
   const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
   const KsimCtx* ctx = args->ctx;
   const dim3 grid((unsigned)n_scen), block(SB);
-  if (spr) {
-    // two instantiations, with and without prefix queues: ABS and WHY are on in both (without node
-    // sets no count is negative, without records why.cap is 0: the same answers)
-    SwgArgsSpr sa{};
-    (SwgArgsPre&)sa = *args;
-    sa.aff = spr->aff;
-    if (args->off)
-      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, true, true>), grid, block, lds, st, ctx, sa);
-    else
-      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, false, true>), grid, block, lds, st, ctx, sa);
-  } else if (args->off) {  // ksim_sweep_drain
-    if (absent && why)
-      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, true>), grid, block, lds, st, ctx, *args);
-    else if (absent)
-      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, false, true>), grid, block, lds, st, ctx, *args);
-    else if (why)
-      hipLaunchKernelGGL((ksim_sweep_general_kernel<false, true, true>), grid, block, lds, st, ctx, *args);
-    else
-      hipLaunchKernelGGL((ksim_sweep_general_kernel<false, false, true>), grid, block, lds, st, ctx, *args);
-  } else if (absent && why)
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true>), grid, block, lds, st, ctx, (const SwgArgsWhy&)*args);
-  else if (absent)
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<true, false>), grid, block, lds, st, ctx, (const SwgArgs&)*args);
-  else if (why)
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, true>), grid, block, lds, st, ctx, (const SwgArgsWhy&)*args);
-  else
-    hipLaunchKernelGGL((ksim_sweep_general_kernel<false, false>), grid, block, lds, st, ctx, (const SwgArgs&)*args);
+  with_flag(args->off != nullptr, [&](auto pre) {
+    constexpr bool PRE = decltype(pre)::value;
+    if (spr) {
+      // two instantiations, with and without prefix queues: ABS and WHY are on in both (without node
+      // sets no count is negative, without records why.cap is 0: the same answers)
+      SwgArgsSpr sa{};
+      (SwgArgsPre&)sa = *args;
+      sa.aff = spr->aff;
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, PRE, true>), grid, block, lds, st, ctx, sa);
+      return;
+    }
+    with_flag(absent != nullptr, [&](auto ABS) {
+      with_flag(why, [&](auto WHY) {
+        hipLaunchKernelGGL((ksim_sweep_general_kernel<decltype(ABS)::value, decltype(WHY)::value, PRE>), grid, block,
+                           lds, st, ctx, *args);
+      });
+    });
+  });
   e = hipGetLastError();
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;
-}
-
-extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsWhy* args,
-                                                int32_t n_scen, const uint32_t* absent, int32_t absent_words,
-                                                int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
-  SwgArgsPre a{};
-  (SwgArgsWhy&)a = *args;
-  return swg_launch(hc, cols, &a, n_scen, absent, absent_words, err, ev0, ev1, st);
-}
-
-// The general form with a prefix queue per scenario (ksim_sweep_drain): args->off / pod / out_pre are
-// the whole sweep's, indexed by args->scen0 + the chunk's scenario.
-extern "C" hipError_t ksim_sweep_drain_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                              int32_t n_scen, const uint32_t* absent, int32_t absent_words,
-                                              int32_t* err, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
-  return swg_launch(hc, cols, args, n_scen, absent, absent_words, err, ev0, ev1, st);
-}
-
-// The general form over a SelectorSpread queue (the SPR instantiations): spr holds the handle's
-// affinity descriptor and the chunk's count copies and per-scenario descriptors; args->off set: with
-// prefix queues (ksim_sweep_drain).
-extern "C" hipError_t ksim_sweep_spread_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                               const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
-                                               int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                                               hipStream_t st) {
-  return swg_launch(hc, cols, args, n_scen, absent, absent_words, err, ev0, ev1, st, spr);
 }
