@@ -267,6 +267,9 @@ extern "C" int ksim_load_affinity(ksim_handle* h, const ksim_affinity_tables* t)
   h->aff_n_carry = t->n_carry;
   h->aff_n_zone = n_zone;
   h->aff_cnt_len = t->cnt_len;
+  h->aff_carried_len = t->carried_len;
+  h->aff_any_spread = false;
+  for (int32_t a = 0; t->spread_pair && a < t->n_aclass; ++a) h->aff_any_spread |= t->spread_pair[a] >= 0;
   h->aff_n_keys = t->n_keys;
   h->pg_id_anti_off = dao; h->pg_id_anti = da; h->pg_id_prio_off = dpo; h->pg_id_prio = dp;
   h->pg_id_mp_off = dmo; h->pg_id_mp = dm;

@@ -46,9 +46,9 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
                                         int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
                                         hipEvent_t ev1, hipStream_t st);
 extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                                const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
-                                                int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                                                hipStream_t st);
+                                                const SwgSpread* spr, const SwgAffinity* ipa, int32_t n_scen,
+                                                const uint32_t* absent, int32_t absent_words, int32_t* err,
+                                                hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
 extern "C" int ksim_pfast_config(int64_t n, int max_grid, int stream, int* grid, int* lds_rows);
 extern "C" hipError_t ksim_pstream_prepare(const KsimCtx* c, double* mirror, hipStream_t s);
 extern "C" size_t ksim_pfast_granule_bytes(void);
@@ -245,6 +245,8 @@ struct ksim_handle {
   uint8_t* aff_aclass_shared = nullptr;
   int32_t aff_n_pair = 0, aff_n_carry = 0, aff_n_zone = 0, aff_n_keys = 0;
   int64_t aff_cnt_len = 0;                 // words of the counted-pair array (a sweep scenario's copy)
+  int64_t aff_carried_len = 0;             // ... and of the carried-term array
+  bool aff_any_spread = false;             // an affinity class has a SelectorSpread pair
   // identity lists for the pod-context records (CSR, device): carried anti / priority terms the
   // identity matches, counted pairs it matches as (pair, key); and the longest list of each kind
   // over identities / affinity classes (the record-size bound)

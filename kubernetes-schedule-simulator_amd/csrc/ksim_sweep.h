@@ -91,6 +91,32 @@ struct SwgSpread {
   KsimAff* aff;     // [C]
 };
 
+// Inter-pod affinity queues (ksim_sweep_affinity, include/ksim_affsweep.h, the IPA instantiations on
+// top of SPR): the tables hold required, preferred or carried terms.  Scenario s of a chunk also owns
+// the s-th [carried_len] copy of the carried-term array (its KsimAff's carried rebased to it), its
+// KsimCtx::aff points at its own KsimAff (MatchInterPodAffinity in the shared predicate chain), and
+// raw is its [n] column of InterPodAffinityPriority's sums between steps 1 and 1b of a pod.  Both
+// copies are the handle's arrays minus the contribution of every resident (the placed pods behind
+// the handle's counts) whose node the scenario does not list: a zone- or cluster-keyed domain counts
+// pods on absent nodes, and the reference removes those pods with their nodes.
+struct SwgArgsIpa : SwgArgsSpr {
+  int64_t* raw;  // [C][n]
+};
+struct SwgResidents {
+  int64_t n;
+  const int32_t* node;       // [n] name rank
+  const int32_t* aff_ident;  // [n] as ksim_pod.aff_ident
+  const int32_t* aff_class;  // [n] as ksim_pod.aff_class
+};
+struct SwgAffinity {
+  int64_t* carried;  // [C][carried_len]
+  int64_t carried_len;
+  int64_t* raw;      // [C][n]
+  SwgResidents res;  // device arrays (n == 0: nothing to correct)
+  int32_t* bad;      // the lowest scenario of the sweep with a negative count after the correction
+};
+#define KSIM_SWEEP_ERR_COUNTS 256  // the sweep's own error word: a scenario's corrected count is negative
+
 // one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
 #define KSIM_SWEEP_GENERAL_MAX_NODES 38400
 #define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word
@@ -104,3 +130,4 @@ static_assert(KSIM_MAX_RCLASS <= 16, "the reduce class takes the low four bits o
 static_assert(sizeof(KsimCtx) + sizeof(SwgArgsWhy) <= 4096 - 64, "KsimCtx + SwgArgs exceed the kernel-argument limit");
 static_assert(sizeof(KsimCtx) + sizeof(SwgArgsPre) <= 4096 - 64, "KsimCtx + SwgArgsPre exceed the kernel-argument limit");
 static_assert(sizeof(KsimCtx) + sizeof(SwgArgsSpr) <= 4096 - 64, "KsimCtx + SwgArgsSpr exceed the kernel-argument limit");
+static_assert(sizeof(KsimCtx) + sizeof(SwgArgsIpa) <= 4096 - 64, "KsimCtx + SwgArgsIpa exceed the kernel-argument limit");

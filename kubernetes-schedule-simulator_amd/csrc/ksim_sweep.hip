@@ -232,6 +232,14 @@ __device__ __forceinline__ SwgSpreadLds& swg_spread_lds() {
   __shared__ SwgSpreadLds l;
   return l;
 }
+// LDS of the IPA instantiations only: each wave's (min, max) raw InterPodAffinityPriority sum
+struct SwgIpaLds {
+  int64_t mm[SW][2];
+};
+__device__ __forceinline__ SwgIpaLds& swg_ipa_lds() {
+  __shared__ SwgIpaLds l;
+  return l;
+}
 constexpr int SWG_AGG_ZONES = 16;  // up to here a wave adds one sum per zone it holds, not one per lane
 }  // namespace
 
@@ -258,11 +266,23 @@ constexpr int SWG_AGG_ZONES = 16;  // up to here a wave adds one sum per zone it
 // committing thread also runs ksim_aff_commit_body on the scenario's counts, for every pod with an
 // identity.  Barriers per pod: 3 with one reduce class and 4 with several, as ever; a pod that reads a
 // spread pair takes one more (4 and 5).  A pod without a pair scores a constant: today's steps.
-template <bool ABS, bool WHY, bool PRE = false, bool SPR = false>
+//
+// IPA (ksim_sweep_affinity, on top of SPR: the tables hold inter-pod affinity terms): the scenario's
+// KsimCtx::aff is its own descriptor, so ksim_predicates_a evaluates MatchInterPodAffinity at its place
+// in predicatesOrdering, in step 1 and in the WHY pass, over the scenario's cnt and carried.  A pod
+// that reads InterPodAffinityPriority (uniform: ksim_interpod_prio_work) stores each fit row's raw sum
+// in the scenario's raw column and keeps the thread's (min, max), both from 0; the block reduction
+// carries them as int64 words, and step 1b adds weight x ksim_interpod_score beside the spread term, if
+// any, before (M, C) or the class maxima are taken.  A thread rereads only the raw words it wrote: no
+// barrier.  A pod that reads either priority, or both, takes step 1b's one barrier more; a pod with
+// neither identity nor class takes exactly the SPR steps.  The commit is ksim_aff_commit_body on both
+// copies.
+template <bool ABS, bool WHY, bool PRE = false, bool SPR = false, bool IPA = false>
 __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
     const KsimCtx* __restrict__ ctxs,
-    const std::conditional_t<SPR, SwgArgsSpr,
-                             std::conditional_t<PRE, SwgArgsPre, std::conditional_t<WHY, SwgArgsWhy, SwgArgs>>> a) {
+    const std::conditional_t<IPA, SwgArgsIpa, std::conditional_t<SPR, SwgArgsSpr,
+                             std::conditional_t<PRE, SwgArgsPre, std::conditional_t<WHY, SwgArgsWhy, SwgArgs>>>> a) {
+  static_assert(SPR || !IPA, "the IPA instantiations extend the SPR ones");
   extern __shared__ uint32_t sg[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
   __shared__ int32_t s_wtot[SW];
@@ -293,8 +313,16 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       zrow = Ap->dom + (int64_t)Ap->zone_key * n;
       nz = Ap->n_zone;  // <= KSIM_SWEEP_SPREAD_MAX_ZONES (host-checked)
     }
+    if constexpr (IPA) {  // more zones are swept when no class has a spread pair: the zone words stay unused
+      if (nz > KSIM_SWEEP_SPREAD_MAX_ZONES) {
+        zrow = nullptr;
+        nz = 0;
+      }
+    }
     for (int z = tid; z < 2 * KSIM_SWEEP_SPREAD_MAX_ZONES; z += SB) (&swg_spread_lds().z[0][0])[z] = 0;
   }
+  int64_t* rawc = nullptr;  // IPA: the scenario's column of raw InterPodAffinityPriority sums
+  if constexpr (IPA) rawc = a.raw + (int64_t)s * n;
   __syncthreads();
   // PRE: the scenario's prefix pre[0 .. m) and the queue index of its step q (uniform)
   int32_t m = 0;
@@ -349,6 +377,15 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       if (sp >= 0) scnt = Ap->cnt + Ap->pair_off[sp];
       zw = swg_spread_lds().z[pb];
     }
+    // IPA: does the pod read InterPodAffinityPriority (uniform)?  The thread's min / max raw sum over
+    // its fit rows, both from 0 (interpod_affinity.go:129-131).  two: the score is completed in step 1b
+    bool ipa = false;
+    int64_t rmn = 0, rmx = 0;
+    if constexpr (IPA) ipa = c.w[KSIM_W_INTERPOD_AFFINITY] != 0 && !c.no_prio && ksim_interpod_prio_work(*Ap, P);
+    auto two = [&]() -> bool {
+      if constexpr (IPA) return sp >= 0 || ipa;
+      return SPR && sp >= 0;
+    };
     // ---- 1. evaluate every row ----
     int32_t f = 0, mx = -1, cm = 0;
     for (int64_t j = tid; j < n; j += SB) {
@@ -381,14 +418,25 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
         int q = 0;
         if (K > 1) {
           q = ksim_rclass_a(P, j, k1, k2, acc);
-          // (SPR, a spread pod: the score is incomplete, the class maximum is taken in step 1b)
-          if ((!SPR || sp < 0) && e > __hip_atomic_load(&s_M[pb][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+          // (SPR, a spread pod: the score is incomplete, the class maximum is taken in step 1b; IPA: of
+          // any pod that takes step 1b.  Kept apart: the other instantiations compile to what they were)
+          bool now = !SPR || sp < 0;
+          if constexpr (IPA) now = !two();
+          if (now && e > __hip_atomic_load(&s_M[pb][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
             atomicMax(&s_M[pb][q], e);
         }
         wd = ((uint32_t)e << 4) | (uint32_t)q;
         f += 1;
         cm = e > mx ? 1 : cm + (e == mx ? 1 : 0);
         mx = e > mx ? e : mx;
+        if constexpr (IPA) {
+          if (ipa) {  // uniform
+            const int64_t raw = ksim_interpod_raw_body(*Ap, P, j);
+            rawc[j] = raw;
+            rmn = raw < rmn ? raw : rmn;
+            rmx = raw > rmx ? raw : rmx;
+          }
+        }
       }
       sg[j] = wd;
       if constexpr (SPR) {
@@ -423,6 +471,12 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
         if (sp >= 0) {  // a spread pod: the maximum count and haveZones in place of (M, C)
           const int32_t Xw = ksimw::max_i32(mxc), Hw = ksimw::max_i32(hzt);
           if (lane == 0) { s_red[wv][1] = Xw; s_red[wv][2] = Hw; }
+        }
+      }
+      if constexpr (IPA) {
+        if (ipa) {
+          const int64_t Nw = ksimw::min_i64(rmn), Xw = ksimw::max_i64(rmx);
+          if (lane == 0) { swg_ipa_lds().mm[wv][0] = Nw; swg_ipa_lds().mm[wv][1] = Xw; }
         }
       }
     }
@@ -478,22 +532,38 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       continue;
     }
     if constexpr (SPR) {
-      if (sp >= 0) {  // ---- 1b. the spread score of the thread's own fit rows, then (M, C) or the class maxima ----
-        const int64_t max_node = (int64_t)ksimw::max_i32(in ? s_red[lane][1] : 0);
-        const bool have_zones = ksimw::max_i32(in ? s_red[lane][2] : 0) != 0;
+      if (two()) {  // ---- 1b. the spread score of the thread's own fit rows, then (M, C) or the class maxima ----
+        // (IPA: and / or their InterPodAffinityPriority score, from the workgroup's min / max raw sum)
+        const bool spread = !IPA || sp >= 0;
+        const int64_t max_node = spread ? (int64_t)ksimw::max_i32(in ? s_red[lane][1] : 0) : 0;
+        const bool have_zones = spread && ksimw::max_i32(in ? s_red[lane][2] : 0) != 0;
         unsigned long long zm = 0;  // every wave: the maximum over all zone words (zones without a fit node hold 0)
-        for (int z = lane; z < nz; z += 64) zm = zw[z] > zm ? zw[z] : zm;
-        const int64_t max_zone = ksimw::max_i64((int64_t)zm);
+        if (spread)
+          for (int z = lane; z < nz; z += 64) zm = zw[z] > zm ? zw[z] : zm;
+        const int64_t max_zone = spread ? ksimw::max_i64((int64_t)zm) : 0;
         const int32_t wsp = (int32_t)c.w[KSIM_W_SELECTOR_SPREAD];
+        int64_t imn = 0, imx = 0;
+        int32_t wip = 0;
+        if constexpr (IPA) {
+          if (ipa) {
+            imn = ksimw::min_i64(in ? swg_ipa_lds().mm[lane][0] : 0);
+            imx = ksimw::max_i64(in ? swg_ipa_lds().mm[lane][1] : 0);
+            wip = (int32_t)c.w[KSIM_W_INTERPOD_AFFINITY];
+          }
+        }
         mx = -1;
         cm = 0;
         for (int64_t j = tid; j < n; j += SB) {
           const uint32_t wd = sg[j];
           if (wd == GNOFIT) continue;
-          const int32_t zj = zrow ? zrow[j] : -1;
+          const int32_t zj = (spread && zrow) ? zrow[j] : -1;
           const int64_t zs = zj >= 0 ? (int64_t)zw[zj] : 0;
           // < 2^27 with the map score (host-checked weights)
-          const int32_t e = (int32_t)(wd >> 4) + wsp * (int32_t)ksim_spread_score(scnt[j], max_node, have_zones, zj, zs, max_zone);
+          int32_t e = (int32_t)(wd >> 4);
+          if (spread) e += wsp * (int32_t)ksim_spread_score(scnt[j], max_node, have_zones, zj, zs, max_zone);
+          if constexpr (IPA) {
+            if (ipa) e += wip * (int32_t)ksim_interpod_score(rawc[j], imn, imx);
+          }
           const uint32_t q = wd & 15u;
           sg[j] = ((uint32_t)e << 4) | q;
           if (K > 1) {
@@ -630,6 +700,45 @@ __global__ void ksim_sweep_spread_init_kernel(const KsimAff base, int32_t* cnt, 
   }
 }
 
+// IPA: every scenario's copy of the carried terms from the handle's current ones; its descriptor (the
+// spread init kernel's, earlier on the stream) gets carried at the copy, its context (the context
+// kernel's) the descriptor
+__global__ void ksim_sweep_affinity_init_kernel(const int64_t* carried0, int64_t* carried, int64_t carried_len, int64_t total,
+                                                int32_t n_scen, KsimAff* aff, KsimCtx* ctx) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < total) carried[k] = carried0[k % carried_len];
+  if (k < n_scen) {
+    aff[k].carried = carried + k * carried_len;
+    ctx[k].aff = aff + k;
+  }
+}
+
+// IPA, after the copies: thread (scenario, resident) takes the resident's contribution out of the
+// scenario's counts and carried terms when its node is absent there (NodeInfo.RemovePod of a pod that
+// the reference never sees).  Node, identity and class are host-checked against the loaded tables.
+__global__ void ksim_sweep_affinity_correct_kernel(const KsimAff* aff, const SwgResidents res, const uint32_t* absent,
+                                                   int32_t words, int64_t total) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= total) return;
+  const int64_t s = k / res.n, r = k % res.n;
+  const int32_t i = res.node[r];
+  if (!((absent[s * words + (i >> 5)] >> (i & 31)) & 1u)) return;
+  ksim_pod P{};
+  P.aff_ident = res.aff_ident[r];
+  P.aff_class = res.aff_class[r];
+  ksim_aff_commit_body(aff[s], P, i, -1);
+}
+
+// IPA, after the correction: a negative count means the residents are not the pods behind the
+// handle's counts -> the sweep's error word, and the lowest such scenario of the whole sweep
+__global__ void ksim_sweep_affinity_check_kernel(const int32_t* cnt, int64_t cnt_len, int64_t total, int32_t scen0,
+                                                 int32_t* err, int32_t* bad) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= total || cnt[k] >= 0) return;
+  atomicOr(err, KSIM_SWEEP_ERR_COUNTS);
+  atomicMin(bad, scen0 + (int32_t)(k / cnt_len));
+}
+
 // static float64 columns, once per handle
 __global__ void ksim_sweep_static_kernel(const int64_t* ac, const int64_t* am, int64_t n, double* dac, double* dam,
                                          double* yc, double* ym) {
@@ -717,10 +826,12 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
 // sweep's, indexed by args->scen0 + the chunk's scenario.
 // spr set: the SPR instantiations (a SelectorSpread queue): the handle's affinity descriptor and the
 // chunk's count copies and per-scenario descriptors.
+// ipa set (with spr): the IPA instantiations (ksim_sweep_affinity): the chunk's carried copies and raw
+// columns, the residents, and the word for the scenario whose corrected counts are negative.
 extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                                const SwgSpread* spr, int32_t n_scen, const uint32_t* absent,
-                                                int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                                                hipStream_t st) {
+                                                const SwgSpread* spr, const SwgAffinity* ipa, int32_t n_scen,
+                                                const uint32_t* absent, int32_t absent_words, int32_t* err,
+                                                hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
   if (spr) {
     const int64_t ct = spr->cnt_len * (int64_t)n_scen, thr = ct > n_scen ? ct : (int64_t)n_scen;
@@ -744,12 +855,32 @@ extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols
   k.err = err;
   hipLaunchKernelGGL(ksim_sweep_general_ctx_kernel, dim3((unsigned)((n_scen + 63) / 64)), dim3(64), 0, st, k, args->w,
                      args->scen0, n_scen, args->ctx);
+  if (ipa) {
+    const int64_t ct = ipa->carried_len * (int64_t)n_scen, thr = ct > n_scen ? ct : (int64_t)n_scen;
+    hipLaunchKernelGGL(ksim_sweep_affinity_init_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st,
+                       spr->base.carried, ipa->carried, ipa->carried_len, ct, n_scen, spr->aff, args->ctx);
+    if (absent && ipa->res.n > 0) {
+      const int64_t rt = ipa->res.n * (int64_t)n_scen, kt = spr->cnt_len * (int64_t)n_scen;
+      hipLaunchKernelGGL(ksim_sweep_affinity_correct_kernel, dim3((unsigned)((rt + 255) / 256)), dim3(256), 0, st, spr->aff,
+                         ipa->res, absent, absent_words, rt);
+      hipLaunchKernelGGL(ksim_sweep_affinity_check_kernel, dim3((unsigned)((kt + 255) / 256)), dim3(256), 0, st, spr->cnt,
+                         spr->cnt_len, kt, args->scen0, err, ipa->bad);
+    }
+  }
   const size_t lds = (size_t)n * sizeof(uint32_t);
   const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
   const KsimCtx* ctx = args->ctx;
   const dim3 grid((unsigned)n_scen), block(SB);
   with_flag(args->off != nullptr, [&](auto pre) {
     constexpr bool PRE = decltype(pre)::value;
+    if (ipa) {  // as the SPR ones: ABS and WHY on
+      SwgArgsIpa ia{};
+      (SwgArgsPre&)ia = *args;
+      ia.aff = spr->aff;
+      ia.raw = ipa->raw;
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, PRE, true, true>), grid, block, lds, st, ctx, ia);
+      return;
+    }
     if (spr) {
       // two instantiations, with and without prefix queues: ABS and WHY are on in both (without node
       // sets no count is negative, without records why.cap is 0: the same answers)

@@ -1,6 +1,6 @@
 // ksim_sweep_rt.cpp — host side of the scenario sweep: ksim_sweep (include/ksim.h),
-// ksim_sweep_nodes, ksim_sweep_explain (include/ksim_whatif.h) and ksim_sweep_drain
-// (include/ksim_drain.h).
+// ksim_sweep_nodes, ksim_sweep_explain (include/ksim_whatif.h), ksim_sweep_drain
+// (include/ksim_drain.h) and ksim_sweep_affinity (include/ksim_affsweep.h).
 //
 // Three forms share one driver: the tree form (ksim_tree.hip) and the scan form (ksim_sweep_kernel)
 // for resource-only ranges, the general form (ksim_sweep_general_kernel) for every other.  A form
@@ -10,6 +10,7 @@
 #include "ksim_handle.h"
 #include "ksim_sweep_plan.h"
 
+#include "../../include/ksim_affsweep.h"
 #include "../../include/ksim_drain.h"
 #include "../../include/ksim_whatif.h"
 
@@ -37,6 +38,10 @@ struct Sweep {
   int32_t* out_rehosted;
   int32_t aw;    // node-set words per scenario
   int32_t wcap;  // records of failed pods a scenario keeps on the device (0: none)
+  // ksim_sweep_affinity: the tables' inter-pod affinity terms are swept (the IPA instantiations), every
+  // scenario's counts less the residents on its absent nodes (res may be null: nothing is corrected)
+  bool ipa = false;
+  const ksim_sweep_residents* res = nullptr;
 
   size_t S() const { return (size_t)n_scen; }
   size_t P() const { return (size_t)count; }
@@ -273,8 +278,18 @@ int sweep_general(Sweep& sw) {
   // A pod with affinity state is swept when that state is SelectorSpread's alone (the SPR
   // instantiations): no affinity / anti-affinity term of any pod class, no term carried by a running
   // pod, no auxiliary or lender tables, and the zones within the kernel's LDS words.
+  // ksim_sweep_affinity (sw.ipa) sweeps those terms too (the IPA instantiations), over every range:
+  // it needs the tables, refuses the zones only where a class has a spread pair (else the zone words
+  // stay unused), and auxiliary or lender tables by the refusal every range gets below.
+  const bool ipa = sw.ipa;
+  if (ipa && !h->have_aff)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: no affinity tables are loaded (ksim_sweep_nodes and ksim_sweep_drain sweep "
+                                       "such a queue)", who);
+  if (ipa && h->aff_n_zone > KSIM_SWEEP_SPREAD_MAX_ZONES && h->aff_any_spread)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %d zones exceed the %d zones of a swept SelectorSpread queue (an affinity "
+                                       "class has a spread pair)", who, h->aff_n_zone, KSIM_SWEEP_SPREAD_MAX_ZONES);
   char spr_no[96] = "";
-  if (h->have_aff) {
+  if (h->have_aff && !ipa) {
     if (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car)
       snprintf(spr_no, sizeof spr_no, " (the tables hold inter-pod affinity terms: only SelectorSpread state is swept)");
     else if (ksim_rt_launch_tables(h))
@@ -283,7 +298,7 @@ int sweep_general(Sweep& sw) {
       snprintf(spr_no, sizeof spr_no, " (%d zones exceed the %d zones of a swept SelectorSpread queue)", h->aff_n_zone,
                KSIM_SWEEP_SPREAD_MAX_ZONES);
   }
-  bool spr = ksim_rt_aff_count(h, first, count) > 0;
+  bool spr = ipa || ksim_rt_aff_count(h, first, count) > 0;
   if (spr && spr_no[0])
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state%s", who, spr_no);
   for (int64_t q = first; q < first + count; ++q)
@@ -320,25 +335,39 @@ int sweep_general(Sweep& sw) {
   if (sw.weights && wspr)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over a SelectorSpread queue would drop the handle's "
                                        "spread priority (weights = NULL sweeps under the whole configured policy)", who);
-  // a packed evaluation holds the map score (and a spread pod's spread score) in
-  // KSIM_SWEEP_GENERAL_SCORE_BITS bits: 10 x (LeastRequested + MostRequested + Balanced + spread weight)
+  // ... and the inter-pod weight of a pod that reads InterPodAffinityPriority
+  const int64_t wipa = (ipa && !c.no_prio) ? c.w[KSIM_W_INTERPOD_AFFINITY] : 0;
+  // a packed evaluation holds the map score (and a pod's spread and inter-pod scores) in
+  // KSIM_SWEEP_GENERAL_SCORE_BITS bits: 10 x (LeastRequested + MostRequested + Balanced + spread weight
+  // + inter-pod weight)
   std::vector<int64_t> w3;
-  if (int rc = sweep_weights(sw, wspr, ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10 - 1, "map scores",
-                             KSIM_SWEEP_GENERAL_SCORE_BITS, &w3))
+  if (int rc = sweep_weights(sw, wspr + wipa, ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10 - 1,
+                             ipa ? "map, spread and inter-pod scores" : "map scores", KSIM_SWEEP_GENERAL_SCORE_BITS, &w3))
     return rc;
   // scratch: a chunk of C scenarios' copies of every column a commit writes, their contexts and
   // outputs, every scenario's weights, the sweep's error word and the whole sweep's prefix queues
   // (off, pod, out_pre: uploaded once, indexed by global scenario); a SelectorSpread queue adds a
-  // scenario's copy of the counted pairs and its affinity descriptor.  One chunk is one launch.
+  // scenario's copy of the counted pairs and its affinity descriptor; ksim_sweep_affinity its copy of
+  // the carried terms and its column of raw priority sums, and the residents (uploaded once).  One
+  // chunk is one launch.
   const size_t S = sw.S(), N = (size_t)n, P = sw.P();
   const size_t NS = (size_t)c.n_scalar, NP = (size_t)c.port_slots;
   const size_t CL = spr ? (size_t)h->aff_cnt_len : 0;
+  const size_t KL = ipa ? (size_t)h->aff_carried_len : 0, R = ipa && sw.res ? (size_t)sw.res->n : 0;
   SwgCols cols{};
   SwgArgsPre a{};
   SwgSpread sprd{};
+  SwgAffinity affd{};
   SweepOut d{};
   int32_t* derr = nullptr;  // ksim_commit's port-slot overflow bit (the handle's word is not written)
   int64_t *dw = nullptr, *doff = nullptr, *dpod = nullptr;
+  int32_t *rnode = nullptr, *rident = nullptr, *rclass = nullptr;
+  auto residents = [&](KsimSweepCarver& cv, size_t) {
+    rnode = cv.take<int32_t>(R);
+    rident = cv.take<int32_t>(R);
+    rclass = cv.take<int32_t>(R);
+    affd.bad = cv.take<int32_t>(1);
+  };
   auto prefix = [&](KsimSweepCarver& cv, size_t) {
     doff = cv.take<int64_t>(S + 1);
     dpod = cv.take<int64_t>(T);
@@ -361,10 +390,16 @@ int sweep_general(Sweep& sw) {
       sprd.cnt = cv.take<int32_t>(C * CL);
       sprd.aff = cv.take<KsimAff>(C);
     }
+    if (ipa) {
+      affd.carried = cv.take<int64_t>(C * KL);
+      affd.raw = cv.take<int64_t>(C * N);
+      residents(cv, C);
+    }
   };
-  const size_t b_rq = rq ? ksim_sweep_measure(prefix, 0) : 0;  // chunk-independent: off the budget first
+  // chunk-independent: off the budget first
+  const size_t b_rq = (rq ? ksim_sweep_measure(prefix, 0) : 0) + (ipa ? ksim_sweep_measure(residents, 0) : 0);
   const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + sw.MW() + why_bytes(sw.wcap) +
-                     (spr ? CL * 4 + sizeof(KsimAff) : 0);
+                     (spr ? CL * 4 + sizeof(KsimAff) : 0) + (ipa ? KL * 8 + N * 8 : 0);
   const int32_t chunk = sweep_scratch(sw, &h->sw_scratch, &h->sw_scratch_bytes, per, b_rq, layout);
   if (!chunk) return KSIM_E_NOMEM;
   a.n_pods = (int32_t)count;
@@ -384,6 +419,17 @@ int sweep_general(Sweep& sw) {
     sprd.base = h->aff_h;
     sprd.cnt_len = (int64_t)CL;
   }
+  if (ipa) {
+    affd.carried_len = (int64_t)KL;
+    affd.res = SwgResidents{(int64_t)R, rnode, rident, rclass};
+    const int32_t none = INT32_MAX;
+    HIPCHK(h, hipMemcpyAsync(affd.bad, &none, 4, hipMemcpyHostToDevice, ksim_stream(h)));
+    if (R) {
+      HIPCHK(h, hipMemcpyAsync(rnode, sw.res->node, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
+      HIPCHK(h, hipMemcpyAsync(rident, sw.res->aff_ident, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
+      HIPCHK(h, hipMemcpyAsync(rclass, sw.res->aff_class, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
+    }
+  }
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
@@ -392,8 +438,8 @@ int sweep_general(Sweep& sw) {
     const int32_t nsc = std::min(chunk, n_scen - s0);
     a.scen0 = s0;  // the chunk's first scenario: its row of the weights
     if (int rc = chunk_absent(sw, d, s0, nsc)) return rc;
-    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, spr ? &sprd : nullptr, nsc, d.absent, sw.aw, derr, h->ev0,
-                                             h->ev1, ksim_stream(h));
+    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, spr ? &sprd : nullptr, ipa ? &affd : nullptr, nsc, d.absent,
+                                             sw.aw, derr, h->ev0, h->ev1, ksim_stream(h));
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
     HIPCHK(h, hipEventSynchronize(h->ev1));
     float c_ms = 0.f;
@@ -403,6 +449,12 @@ int sweep_general(Sweep& sw) {
   }
   int32_t err = 0;
   HIPCHK(h, hipMemcpy(&err, derr, 4, hipMemcpyDeviceToHost));
+  if (err & KSIM_SWEEP_ERR_COUNTS) {
+    int32_t bad = 0;
+    HIPCHK(h, hipMemcpy(&bad, affd.bad, 4, hipMemcpyDeviceToHost));
+    return ksim_fail(h, KSIM_E_INVAL, "%s: scenario %d: a counted pair is negative once the residents of its absent nodes "
+                                 "are taken out (the residents are not the placed pods behind the handle's counts)", who, bad);
+  }
   if (err)
     return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's host-port slots overflowed in a scenario (load the node table with "
                                     "more port slots)", who);
@@ -620,6 +672,34 @@ int check_failures(ksim_handle* h, const char* who, const ksim_sweep_failures* f
   return KSIM_OK;
 }
 
+// ksim_sweep_drain, ksim_sweep_affinity: the scenarios' queues (rq null: the range alone), by what needs
+// no device, before the handle is touched
+int check_queue(ksim_handle* h, const char* who, int32_t n_scen, const ksim_sweep_requeue* rq, bool need_rq, int64_t first,
+                int64_t count, int32_t* out_node) {
+  if (n_scen <= 0 || first < 0 || count < 0 || (!rq && !need_rq && (count == 0 || count > INT32_MAX)))
+    return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
+  if ((need_rq && !rq) || (rq && !rq->off)) return ksim_fail(h, KSIM_E_INVAL, "%s: null re-queue lists", who);
+  if (rq && rq->off[0] != 0) return ksim_fail(h, KSIM_E_INVAL, "%s: off[0] must be 0", who);
+  for (int32_t s = 0; rq && s < n_scen; ++s) {
+    if (rq->off[s + 1] < rq->off[s]) return ksim_fail(h, KSIM_E_INVAL, "%s: off decreases at scenario %d", who, s);
+    if (rq->off[s + 1] - rq->off[s] > (int64_t)INT32_MAX - count)
+      return ksim_fail(h, KSIM_E_INVAL, "%s: the queue of scenario %d exceeds INT32_MAX pods", who, s);
+  }
+  const int64_t T = rq ? rq->off[n_scen] : 0;
+  if (T > 0 && (!rq->pod || !rq->out_node))
+    return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pods without a pod or out_node array", who);
+  if (T == 0 && count == 0) return ksim_fail(h, KSIM_E_INVAL, "%s: neither re-queued pods nor a pod range", who);
+  if (count > 0 && !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
+  if (!h) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
+  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
+  if (first + count > h->n_pods) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
+  for (int64_t k = 0; k < T; ++k)
+    if (rq->pod[k] < 0 || rq->pod[k] >= h->n_pods)
+      return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pod index %lld outside the loaded queue of %lld pods", who,
+                  (long long)rq->pod[k], (long long)h->n_pods);
+  return KSIM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -648,33 +728,50 @@ int ksim_sweep_drain(ksim_handle* h, const uint32_t* absent, int32_t n_scen, con
                      int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
                      int32_t* out_rehosted, const ksim_sweep_failures* fail, ksim_stats* st) {
   const char* who = "ksim_sweep_drain";
-  // what needs no device, before the handle is touched
   if (int rc = check_failures(h, who, fail)) return rc;
-  if (n_scen <= 0 || first < 0 || count < 0) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
-  if (!rq || !rq->off) return ksim_fail(h, KSIM_E_INVAL, "%s: null re-queue lists", who);
-  if (rq->off[0] != 0) return ksim_fail(h, KSIM_E_INVAL, "%s: off[0] must be 0", who);
-  for (int32_t s = 0; s < n_scen; ++s) {
-    if (rq->off[s + 1] < rq->off[s]) return ksim_fail(h, KSIM_E_INVAL, "%s: off decreases at scenario %d", who, s);
-    if (rq->off[s + 1] - rq->off[s] > (int64_t)INT32_MAX - count)
-      return ksim_fail(h, KSIM_E_INVAL, "%s: the queue of scenario %d exceeds INT32_MAX pods", who, s);
-  }
-  const int64_t T = rq->off[n_scen];
-  if (T > 0 && (!rq->pod || !rq->out_node))
-    return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pods without a pod or out_node array", who);
-  if (T == 0 && count == 0) return ksim_fail(h, KSIM_E_INVAL, "%s: neither re-queued pods nor a pod range", who);
-  if (count > 0 && !out_node) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
-  if (!h) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
-  if (!h->have_pods) return ksim_fail(h, KSIM_E_STATE, "%s: load nodes, classes and pods first", who);
-  if (first + count > h->n_pods) return ksim_fail(h, KSIM_E_INVAL, "%s: bad scenario count or pod range", who);
-  for (int64_t k = 0; k < T; ++k)
-    if (rq->pod[k] < 0 || rq->pod[k] >= h->n_pods)
-      return ksim_fail(h, KSIM_E_INVAL, "%s: re-queued pod index %lld outside the loaded queue of %lld pods", who,
-                  (long long)rq->pod[k], (long long)h->n_pods);
+  if (int rc = check_queue(h, who, n_scen, rq, true, first, count, out_node)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
   if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
   Sweep sw{h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq, out_rehosted};
   sw.aw = (int32_t)((h->ctx.n + 31) / 32);
+  return sweep_general(sw);
+}
+
+int ksim_sweep_affinity(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_residents* res,
+                        const ksim_sweep_requeue* rq, int64_t first, int64_t count, int32_t* out_node,
+                        uint64_t* out_counters, int32_t* out_scheduled, int32_t* out_rehosted,
+                        const ksim_sweep_failures* fail, ksim_stats* st) {
+  const char* who = "ksim_sweep_affinity";
+  if (int rc = check_failures(h, who, fail)) return rc;
+  if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
+  if (h->have_aff && h->aff_stale)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the affinity tables predate a node event; load them again", who);
+  if (h->have_vol && h->vol_stale)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the volume tables predate a node event; load them again", who);
+  if (res && res->n < 0) return ksim_fail(h, KSIM_E_INVAL, "%s: a negative number of residents", who);
+  if (res && res->n > 0) {
+    if (!res->node || !res->aff_ident || !res->aff_class)
+      return ksim_fail(h, KSIM_E_INVAL, "%s: residents without a node, aff_ident or aff_class array", who);
+    // (without tables the call is refused below; the bounds are then the empty tables')
+    const int32_t ni = h->have_aff ? h->aff_n_ident : 0, na = h->have_aff ? h->aff_n_aclass : 0;
+    for (int64_t k = 0; k < res->n; ++k) {
+      if (res->node[k] < 0 || res->node[k] >= h->ctx.n)
+        return ksim_fail(h, KSIM_E_INVAL, "%s: resident %lld: node %d outside [0, %lld)", who, (long long)k, res->node[k],
+                    (long long)h->ctx.n);
+      if (res->aff_ident[k] < 0 || res->aff_ident[k] > ni || res->aff_class[k] < 0 || res->aff_class[k] > na)
+        return ksim_fail(h, KSIM_E_INVAL, "%s: resident %lld: identity %d or class %d beyond the loaded tables (%d, %d)", who,
+                    (long long)k, res->aff_ident[k], res->aff_class[k], ni, na);
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
+  if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
+  Sweep sw{h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
+           rq ? out_rehosted : nullptr};
+  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
+  sw.ipa = true;
+  sw.res = res;
   return sweep_general(sw);
 }
 

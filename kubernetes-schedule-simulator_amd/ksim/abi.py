@@ -142,6 +142,11 @@ class SweepRequeue(C.Structure):
     _fields_ = [("off", _i64p), ("pod", _i64p), ("out_node", _i32p)]
 
 
+class SweepResidents(C.Structure):
+    """ksim_sweep_residents (include/ksim_affsweep.h): the placed pods behind the handle's counts."""
+    _fields_ = [("n", C.c_int64), ("node", _i32p), ("aff_ident", _i32p), ("aff_class", _i32p)]
+
+
 SCHEDULE_ONLY, SCHEDULE_ASSUME = 0, 1
 
 
@@ -267,6 +272,10 @@ def lib():
     L.ksim_sweep_drain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepRequeue), C.c_int64, C.c_int64,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SweepFailures),
                                    C.POINTER(Stats)]
+    # include/ksim_affsweep.h (likewise)
+    L.ksim_sweep_affinity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepResidents),
+                                      C.POINTER(SweepRequeue), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(Stats)]
     podargs = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     L.ksim_schedule_one.argtypes = [C.c_void_p] + podargs + [C.c_int32, C.POINTER(Result)]
     L.ksim_pod_add.argtypes = [C.c_void_p, C.c_int64] + podargs

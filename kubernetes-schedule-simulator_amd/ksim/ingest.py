@@ -360,6 +360,7 @@ class Cluster:
         self.image_locality = False
         self.bad_affinity_classes = set()   # preferred terms that fail to parse
         self.affinity = None     # inter-pod affinity tables (ksim/affinity.py), None without terms
+        self.residents = np.zeros((0, 3), np.int32)  # (node, aff_ident, aff_class) of the running pods in its counts
         self.hard_weight = 10
         self.volume_index = None  # ksim/volumes.py VolumeIndex when a pod has predicate volumes
         self.volumes = None       # its device tables (volumes.build_tables)
@@ -615,6 +616,14 @@ class Cluster:
         run_nodes = [self.index[_spec(p)["nodeName"]] for p in running]
         self.affinity, remap = idx.build(run_nodes, idents, aclasses)
         k = len(running)
+        # the running pods as the tables' counts hold them: (node rank, aff_ident, aff_class) per pod
+        # with either, the residents of a sweep over these tables (include/ksim_affsweep.h)
+        res = np.zeros((k, 3), np.int32)
+        if k:
+            res[:, 0] = run_nodes
+            res[:, 1] = remap[np.asarray(idents[:k], np.int64)]
+            res[:, 2] = np.asarray(aclasses[:k], np.int32) + 1
+        self.residents = np.ascontiguousarray(res[(res[:, 1] > 0) | (res[:, 2] > 0)])
         if len(pods):
             self.pods["aff_ident"] = remap[np.asarray(idents[k:], np.int64)]
             self.pods["aff_class"] = np.asarray(aclasses[k:], np.int32) + 1

@@ -640,6 +640,76 @@ class GenericScheduler:
             self.last_failures = fails
         return out, [pre[off[k]:off[k + 1]] for k in range(S)], ctr, st
 
+    def has_affinity_terms(self):
+        """The loaded affinity tables hold an inter-pod affinity term — required, preferred or carried —
+        and not SelectorSpread state alone: sweep / sweep_drain refuse such tables, sweep_affinity
+        sweeps them."""
+        a = self.affinity
+        return a is not None and bool(a["n_terms"] or a["n_carry"] or a["n_carries"])
+
+    def sweep_affinity(self, absent, requeue=None, first=0, count=None, explain=None, bound=()):
+        """Outage and drain what-ifs over inter-pod affinity queues (ksim_sweep_affinity,
+        include/ksim_affsweep.h): sweep(None, absent=...) when requeue is None and sweep_drain(absent,
+        requeue, ...) otherwise, on tables that hold inter-pod affinity terms.  Every scenario runs
+        under the whole policy — MatchInterPodAffinity, InterPodAffinityPriority and SelectorSpread
+        included — on its own copy of the counted pairs and carried terms, from which the placed pods
+        on its absent nodes are taken out: the cluster's running pods, and bound, the (queue index,
+        node rank) pairs an earlier schedule() on this scheduler committed (every bound pod with
+        affinity state must be given, or the call fails with E_INVAL once a count turns negative).
+        Returns what sweep returns (requeue None) or what sweep_drain returns; last_scheduled,
+        last_rehosted and last_failures as there.  Always the general form.  Refused
+        (KsimUnsupported): no affinity tables, volumes on a swept pod, auxiliary or lender tables,
+        more than abi.MAX_RCLASS reduce classes, more than abi.SWEEP_SPREAD_MAX_ZONES zones with
+        SelectorSpread state, a node-sharded scheduler, more than abi.SWEEP_GENERAL_MAX_NODES nodes."""
+        n = len(self._pods)
+        count = n - first if count is None else count
+        mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
+        if requeue is None and mask is None:
+            raise abi.KsimError(abi.E_INVAL, "sweep_affinity: neither absent sets nor re-queue lists")
+        S = len(requeue) if requeue is not None else len(mask)
+        if mask is not None and len(mask) != S:
+            raise abi.KsimError(abi.E_INVAL, "sweep_affinity: %d re-queue lists but %d absent sets" % (S, len(mask)))
+        res = [np.asarray(self.cluster.residents, np.int32).reshape(-1, 3)]
+        for q, w in bound:
+            p = self._pods[int(q)]
+            if p["aff_ident"] > 0 or p["aff_class"] > 0:
+                res.append(np.array([[int(w), p["aff_ident"], p["aff_class"]]], np.int32))
+        res = np.concatenate(res)
+        cols = [np.ascontiguousarray(res[:, k]) for k in range(3)]
+        rs = abi.SweepResidents(len(res), *(abi.ptr(c, C.c_int32) for c in cols))
+        rq = pre = off = None
+        if requeue is not None:
+            requeue = [np.asarray(list(r), np.int64).reshape(-1) for r in requeue]
+            off = np.zeros(S + 1, np.int64)
+            off[1:] = np.cumsum([len(r) for r in requeue])
+            pod = np.ascontiguousarray(np.concatenate(requeue)) if S and off[-1] else np.zeros(0, np.int64)
+            pre = np.zeros(len(pod), np.int32)
+            rq = C.byref(abi.SweepRequeue(abi.ptr(off, C.c_int64), abi.ptr(pod, C.c_int64), abi.ptr(pre, C.c_int32)))
+        out = np.zeros((S, max(count, 0)), np.int32)
+        ctr = np.zeros(S, np.uint64)
+        sched = np.zeros(S, np.int32)
+        rehosted = np.zeros(S, np.int32)
+        f = fails = None
+        if explain is not None and explain is not False:
+            longest = int(np.diff(off).max()) if off is not None and S else 0
+            cap = longest + count if explain is True else int(explain)
+            fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
+                         pod=np.full((S, max(cap, 0)), -1, np.int32),
+                         hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
+            f = C.byref(abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
+                                          abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32)))
+        st = abi.Stats()
+        self.h.call("ksim_sweep_affinity", abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out), abi.vptr(ctr),
+                    abi.vptr(sched), abi.vptr(rehosted), f, C.byref(st))
+        self.last_stats = st
+        self.last_scheduled = sched
+        if fails is not None:
+            self.last_failures = fails
+        if requeue is None:
+            return out, ctr, st
+        self.last_rehosted = rehosted
+        return out, [pre[off[k]:off[k + 1]] for k in range(S)], ctr, st
+
     def evaluate(self, pod):
         """Per-node (fit, reason mask, map score, reduce class) for one loaded pod (no commit)."""
         n = self.cluster.n_nodes
@@ -990,8 +1060,11 @@ class ClusterCapacity:
         state a run() left), on a scheduler of its own.  Queues with node selectors, tolerations,
         host ports, nodeName and gpu / ephemeral / extended requests are swept under the whole
         provider or policy, and with spread= listers under SelectorSpreadPriority /
-        ServiceSpreadingPriority, reduced over each outage's own fit nodes; queues with inter-pod
-        affinity or volume state are refused (KsimUnsupported), as by GenericScheduler.sweep.
+        ServiceSpreadingPriority, reduced over each outage's own fit nodes.  A snapshot with inter-pod
+        affinity terms (required, preferred, or carried by a running pod) is swept through
+        GenericScheduler.sweep_affinity: every outage evaluates MatchInterPodAffinity and
+        InterPodAffinityPriority on its own counts, without the running pods of its lost nodes.
+        Queues with volume state are refused (KsimUnsupported), as by GenericScheduler.sweep.
         Returns one record per outage: dict(name, absent (node count), scheduled, failed,
         placements [(pod name, node name or None)] in queue order).
         explain (ksim_sweep_explain): True, or an int cap per outage — each record gains listed (the
@@ -1016,7 +1089,10 @@ class ClusterCapacity:
         predicates, priorities, kw = self._sched_args
         g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
         try:
-            out, _, _ = g.sweep(None, first, count, absent=sets_, explain=explain if explain else None)
+            if g.has_affinity_terms():  # inter-pod affinity terms: every outage owns its affinity state
+                out, _, _ = g.sweep_affinity(sets_, None, first, count, explain=explain if explain else None)
+            else:
+                out, _, _ = g.sweep(None, first, count, absent=sets_, explain=explain if explain else None)
             fails = g.last_failures if explain else None
         finally:
             g.close()
@@ -1049,8 +1125,9 @@ class ClusterCapacity:
         running pods, the queue followed by the copy of every evictable pod on a node of any outage,
         built with the constructor's listers and policy — and on a scheduler of its own.  With spread=
         listers the evicted pods of a service or controller are re-hosted under the spread priority, as
-        the queue is.  Queues and evicted pods with inter-pod affinity or volume state are refused
-        (KsimUnsupported).
+        the queue is, and with inter-pod affinity terms in the snapshot both are swept through
+        GenericScheduler.sweep_affinity, as in what_if.  Queues and evicted pods with volume state are
+        refused (KsimUnsupported).
         first / count select the queue's range as in what_if (count=0: only re-host).
         Returns one record per outage: dict(name, absent (node count), evicted, rehosted, stranded,
         requeued [(pod name, node name or None)] in eviction order, scheduled, failed, placements
@@ -1087,7 +1164,8 @@ class ClusterCapacity:
         predicates, priorities, kw = self._sched_args
         g = GenericScheduler(dcl, predicates, priorities, collect_reasons=False, **kw)
         try:
-            out, pre, _, _ = g.sweep_drain(sets_, requeue, first, count, explain=explain if explain else None)
+            drain = g.sweep_affinity if g.has_affinity_terms() else g.sweep_drain
+            out, pre, _, _ = drain(sets_, requeue, first, count, explain=explain if explain else None)
             fails = g.last_failures if explain else None
         finally:
             g.close()
