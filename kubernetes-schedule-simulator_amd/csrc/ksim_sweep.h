@@ -117,6 +117,21 @@ struct SwgAffinity {
 };
 #define KSIM_SWEEP_ERR_COUNTS 256  // the sweep's own error word: a scenario's corrected count is negative
 
+// Volume queues (ksim_sweep_volumes, include/ksim_volsweep.h, the VOL instantiations beside the plain,
+// SPR and IPA ones): a range or prefix pod may mount volumes.  Scenario s of a chunk owns the s-th
+// [vol_slots][n] copy of the mount words (the slot stride stays n), the s-th [n] copy of the slot
+// counts and a KsimVol of its own: the handle's with both pointers rebased, the static tables
+// (key_filter, vc, vc_filter, refs, zone_ok) shared.  Its KsimCtx::vol points at that descriptor, so
+// the shared predicate chain evaluates NoDiskConflict, the MaxPD filters and NoVolumeZoneConflict over
+// the scenario's mounts, and the commit writes them.  Mounts are per node and an absent node is never
+// evaluated: no correction.  The kernels take no argument of their own for it.
+struct SwgVolumes {
+  KsimVol base;         // the handle's descriptor (host copy)
+  uint64_t* slots;      // [C][vol_slots][n]
+  int32_t* slot_count;  // [C][n]
+  KsimVol* vol;         // [C]
+};
+
 // one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
 #define KSIM_SWEEP_GENERAL_MAX_NODES 38400
 #define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word

@@ -277,12 +277,22 @@ constexpr int SWG_AGG_ZONES = 16;  // up to here a wave adds one sum per zone it
 // barrier.  A pod that reads either priority, or both, takes step 1b's one barrier more; a pod with
 // neither identity nor class takes exactly the SPR steps.  The commit is ksim_aff_commit_body on both
 // copies.
-template <bool ABS, bool WHY, bool PRE = false, bool SPR = false, bool IPA = false>
+//
+// VOL (ksim_sweep_volumes, beside the plain, SPR and IPA forms with ABS and WHY on: a range or prefix
+// pod may mount volumes): the scenario's KsimCtx::vol is its own descriptor over its own mounts
+// (ksim_sweep_volume_init_kernel), so ksim_predicates_a evaluates NoDiskConflict, the MaxPD filters and
+// NoVolumeZoneConflict at their places in predicatesOrdering, in step 1 and in the WHY pass, as it does
+// in every instantiation whenever vol is set.  The one difference to the parent instantiation: the
+// committing thread also adds the pod's mounts to the chosen node's slots (ksim_vol_commit_body, +1) after
+// ksim_commit, and the closing barrier publishes them with the columns.  A full node or a saturated
+// mount count sets bit 1 of the sweep's own error word, the bit of ksim_commit's port slots.
+template <bool ABS, bool WHY, bool PRE = false, bool SPR = false, bool IPA = false, bool VOL = false>
 __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
     const KsimCtx* __restrict__ ctxs,
     const std::conditional_t<IPA, SwgArgsIpa, std::conditional_t<SPR, SwgArgsSpr,
                              std::conditional_t<PRE, SwgArgsPre, std::conditional_t<WHY, SwgArgsWhy, SwgArgs>>>> a) {
   static_assert(SPR || !IPA, "the IPA instantiations extend the SPR ones");
+  static_assert(!VOL || (ABS && WHY), "the VOL instantiations have ABS and WHY on");
   extern __shared__ uint32_t sg[];  // [n] evaluations of the current pod
   __shared__ int32_t s_red[SW][3];
   __shared__ int32_t s_wtot[SW];
@@ -643,12 +653,17 @@ __global__ __launch_bounds__(SB) void ksim_sweep_general_kernel(
       if constexpr (SPR) {  // NodeInfo.AddPod on the scenario's counts: every pod with an identity
         if (jsel >= 0) ksim_aff_commit_body(*Ap, P, jsel, +1);
       }
+      if constexpr (VOL) {  // ... and on the scenario's mounts: every pod with a volume class
+        if (jsel >= 0 && ksim_is_vol_pod(c, P)) ksim_vol_commit_body(*c.vol, P, jsel, +1, c.err);
+      }
       *answer_of(p) = (int32_t)jsel;
     }
     __syncthreads();  // the commit (workgroup release/acquire) before the next pod's loads
   }
   if (tid == 0) a.out_counter[s] = counter;
 }
+
+#ifndef KSIM_SWEEP_VOL_TU  // (ksim_sweep_vol.hip takes the file down to here and its own launcher at the end)
 
 // Scenario s of the chunk gets its context: k (the handle's, its dynamic columns at the chunk's
 // first copy, err at the sweep's own word) rebased to the scenario's copies, nothing of the per-pod,
@@ -710,6 +725,23 @@ __global__ void ksim_sweep_affinity_init_kernel(const int64_t* carried0, int64_t
   if (k < n_scen) {
     aff[k].carried = carried + k * carried_len;
     ctx[k].aff = aff + k;
+  }
+}
+
+// VOL: every scenario's copy of the mount words and slot counts from the handle's current mounts, its
+// descriptor (the handle's, both pointers at the copies: the slot stride stays n, the static tables are
+// shared) and, after the context kernel on the stream, its context's vol
+__global__ void ksim_sweep_volume_init_kernel(const KsimVol base, uint64_t* slots, int32_t* slot_count, int64_t slot_words,
+                                              int32_t n_scen, KsimVol* out, KsimCtx* ctx) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < slot_words * n_scen) slots[k] = base.slots[k % slot_words];
+  if (k < base.n * n_scen) slot_count[k] = base.slot_count[k % base.n];
+  if (k < n_scen) {
+    KsimVol& V = out[k];
+    V = base;
+    V.slots = slots + k * slot_words;
+    V.slot_count = slot_count + k * base.n;
+    ctx[k].vol = out + k;
   }
 }
 
@@ -820,6 +852,13 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
   return e;
 }
 
+// The VOL instantiations live in a translation unit of their own (ksim_sweep_vol.hip, which takes this
+// file down to the end of the kernel template): instantiating them beside the others changes the code
+// the compiler emits for every existing ksim_sweep_general_kernel, and those are kept instruction for
+// instruction.
+extern "C" hipError_t ksim_sweep_general_vol_launch(const SwgArgsPre* args, const SwgSpread* spr, const SwgAffinity* ipa,
+                                                    int32_t n_scen, size_t lds, hipStream_t st);
+
 // The general form: hc the handle's context, cols the chunk's scenario columns, err the sweep's own
 // error word (ksim_commit's port-slot overflow bit; the handle's word is never written).
 // args->off set: the PRE instantiations (ksim_sweep_drain); off / pod / out_pre are the whole
@@ -828,8 +867,11 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
 // chunk's count copies and per-scenario descriptors.
 // ipa set (with spr): the IPA instantiations (ksim_sweep_affinity): the chunk's carried copies and raw
 // columns, the residents, and the word for the scenario whose corrected counts are negative.
+// vol set (alone, with spr, or with spr and ipa): the VOL instantiations (ksim_sweep_volumes): the
+// handle's volume descriptor and the chunk's mount copies and per-scenario descriptors.
 extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                                const SwgSpread* spr, const SwgAffinity* ipa, int32_t n_scen,
+                                                const SwgSpread* spr, const SwgAffinity* ipa, const SwgVolumes* vol,
+                                                int32_t n_scen,
                                                 const uint32_t* absent, int32_t absent_words, int32_t* err,
                                                 hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
@@ -867,10 +909,20 @@ extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols
                          spr->cnt_len, kt, args->scen0, err, ipa->bad);
     }
   }
+  if (vol) {
+    const int64_t sw = (int64_t)vol->base.vol_slots * n, mt = (sw > n ? sw : n) * n_scen;
+    hipLaunchKernelGGL(ksim_sweep_volume_init_kernel, dim3((unsigned)((mt + 255) / 256)), dim3(256), 0, st, vol->base,
+                       vol->slots, vol->slot_count, sw, n_scen, vol->vol, args->ctx);
+  }
   const size_t lds = (size_t)n * sizeof(uint32_t);
   const bool why = args->why.cap > 0;  // ksim_sweep_explain keeping records
   const KsimCtx* ctx = args->ctx;
   const dim3 grid((unsigned)n_scen), block(SB);
+  if (vol) {  // the VOL instantiations (ksim_sweep_vol.hip)
+    e = ksim_sweep_general_vol_launch(args, spr, ipa, n_scen, lds, st);
+    if (ev1) (void)hipEventRecord(ev1, st);
+    return e;
+  }
   with_flag(args->off != nullptr, [&](auto pre) {
     constexpr bool PRE = decltype(pre)::value;
     if (ipa) {  // as the SPR ones: ABS and WHY on
@@ -901,3 +953,35 @@ extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols
   if (ev1) (void)hipEventRecord(ev1, st);
   return e;
 }
+
+#else  // KSIM_SWEEP_VOL_TU
+
+// The six VOL instantiations: <1, 1, PRE, SPR, IPA, 1> for (SPR, IPA) = (0, 0), (1, 0), (1, 1), chosen as
+// ksim_sweep_general_launch chooses their parents; ABS and WHY are on in all of them.
+extern "C" hipError_t ksim_sweep_general_vol_launch(const SwgArgsPre* args, const SwgSpread* spr, const SwgAffinity* ipa,
+                                                    int32_t n_scen, size_t lds, hipStream_t st) {
+  const KsimCtx* ctx = args->ctx;
+  const dim3 grid((unsigned)n_scen), block(SB);
+  auto launch = [&](auto pre) {
+    constexpr bool PRE = decltype(pre)::value;
+    if (ipa) {
+      SwgArgsIpa ia{};
+      (SwgArgsPre&)ia = *args;
+      ia.aff = spr->aff;
+      ia.raw = ipa->raw;
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, PRE, true, true, true>), grid, block, lds, st, ctx, ia);
+    } else if (spr) {
+      SwgArgsSpr sa{};
+      (SwgArgsPre&)sa = *args;
+      sa.aff = spr->aff;
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, PRE, true, false, true>), grid, block, lds, st, ctx, sa);
+    } else {
+      hipLaunchKernelGGL((ksim_sweep_general_kernel<true, true, PRE, false, false, true>), grid, block, lds, st, ctx, *args);
+    }
+  };
+  if (args->off != nullptr) launch(std::true_type{});
+  else launch(std::false_type{});
+  return hipGetLastError();
+}
+
+#endif  // KSIM_SWEEP_VOL_TU

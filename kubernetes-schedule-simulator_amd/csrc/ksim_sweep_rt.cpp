@@ -1,6 +1,7 @@
 // ksim_sweep_rt.cpp — host side of the scenario sweep: ksim_sweep (include/ksim.h),
 // ksim_sweep_nodes, ksim_sweep_explain (include/ksim_whatif.h), ksim_sweep_drain
-// (include/ksim_drain.h) and ksim_sweep_affinity (include/ksim_affsweep.h).
+// (include/ksim_drain.h), ksim_sweep_affinity (include/ksim_affsweep.h) and ksim_sweep_volumes
+// (include/ksim_volsweep.h).
 //
 // Three forms share one driver: the tree form (ksim_tree.hip) and the scan form (ksim_sweep_kernel)
 // for resource-only ranges, the general form (ksim_sweep_general_kernel) for every other.  A form
@@ -12,6 +13,7 @@
 
 #include "../../include/ksim_affsweep.h"
 #include "../../include/ksim_drain.h"
+#include "../../include/ksim_volsweep.h"
 #include "../../include/ksim_whatif.h"
 
 namespace {
@@ -42,6 +44,9 @@ struct Sweep {
   // scenario's counts less the residents on its absent nodes (res may be null: nothing is corrected)
   bool ipa = false;
   const ksim_sweep_residents* res = nullptr;
+  // ksim_sweep_volumes: range and prefix pods may mount volumes (the VOL instantiations), every scenario
+  // on its own copy of the mounts; affinity terms in the tables are swept as by ksim_sweep_affinity
+  bool vol = false;
 
   size_t S() const { return (size_t)n_scen; }
   size_t P() const { return (size_t)count; }
@@ -281,7 +286,13 @@ int sweep_general(Sweep& sw) {
   // ksim_sweep_affinity (sw.ipa) sweeps those terms too (the IPA instantiations), over every range:
   // it needs the tables, refuses the zones only where a class has a spread pair (else the zone words
   // stay unused), and auxiliary or lender tables by the refusal every range gets below.
-  const bool ipa = sw.ipa;
+  // ksim_sweep_volumes (sw.vol) takes the IPA instantiations when the tables hold such terms, and else
+  // the SPR or plain ones by the rule of every range; it needs the volume tables.
+  const bool terms = h->have_aff && (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car);
+  const bool ipa = sw.ipa || (sw.vol && terms);
+  if (sw.vol && !h->have_vol)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: no volume tables are loaded (ksim_sweep_nodes, ksim_sweep_drain and "
+                                       "ksim_sweep_affinity sweep such a queue)", who);
   if (ipa && !h->have_aff)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: no affinity tables are loaded (ksim_sweep_nodes and ksim_sweep_drain sweep "
                                        "such a queue)", who);
@@ -290,7 +301,7 @@ int sweep_general(Sweep& sw) {
                                        "class has a spread pair)", who, h->aff_n_zone, KSIM_SWEEP_SPREAD_MAX_ZONES);
   char spr_no[96] = "";
   if (h->have_aff && !ipa) {
-    if (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car)
+    if (terms)
       snprintf(spr_no, sizeof spr_no, " (the tables hold inter-pod affinity terms: only SelectorSpread state is swept)");
     else if (ksim_rt_launch_tables(h))
       snprintf(spr_no, sizeof spr_no, " (auxiliary spreading priority or lender tables are loaded)");
@@ -301,7 +312,7 @@ int sweep_general(Sweep& sw) {
   bool spr = ipa || ksim_rt_aff_count(h, first, count) > 0;
   if (spr && spr_no[0])
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state%s", who, spr_no);
-  for (int64_t q = first; q < first + count; ++q)
+  for (int64_t q = first; !sw.vol && q < first + count; ++q)
     if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: pod %lld mounts volumes", who, (long long)q);
   if (ksim_rt_launch_tables(h))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: an auxiliary spreading priority or CheckServiceAffinity's lender table is "
@@ -320,7 +331,8 @@ int sweep_general(Sweep& sw) {
                       (long long)q, spr_no);
         spr = true;
       }
-      if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld mounts volumes", who, (long long)q);
+      if (!sw.vol && h->q_vclass[q])
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld mounts volumes", who, (long long)q);
       if (ksim_rt_range_wide(h, q, 1))
         return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the class of re-queued pod %lld has more than %d reduce classes", who,
                     (long long)q, KSIM_MAX_RCLASS);
@@ -348,8 +360,9 @@ int sweep_general(Sweep& sw) {
   // outputs, every scenario's weights, the sweep's error word and the whole sweep's prefix queues
   // (off, pod, out_pre: uploaded once, indexed by global scenario); a SelectorSpread queue adds a
   // scenario's copy of the counted pairs and its affinity descriptor; ksim_sweep_affinity its copy of
-  // the carried terms and its column of raw priority sums, and the residents (uploaded once).  One
-  // chunk is one launch.
+  // the carried terms and its column of raw priority sums, and the residents (uploaded once);
+  // ksim_sweep_volumes a scenario's copy of the mount words and slot counts and its volume descriptor.
+  // One chunk is one launch.
   const size_t S = sw.S(), N = (size_t)n, P = sw.P();
   const size_t NS = (size_t)c.n_scalar, NP = (size_t)c.port_slots;
   const size_t CL = spr ? (size_t)h->aff_cnt_len : 0;
@@ -358,8 +371,11 @@ int sweep_general(Sweep& sw) {
   SwgArgsPre a{};
   SwgSpread sprd{};
   SwgAffinity affd{};
+  SwgVolumes vold{};
+  const size_t VS = sw.vol ? (size_t)h->vol_h.vol_slots : 0;
   SweepOut d{};
-  int32_t* derr = nullptr;  // ksim_commit's port-slot overflow bit (the handle's word is not written)
+  // ksim_commit's port-slot overflow bit, and the mount commit's (the handle's word is not written)
+  int32_t* derr = nullptr;
   int64_t *dw = nullptr, *doff = nullptr, *dpod = nullptr;
   int32_t *rnode = nullptr, *rident = nullptr, *rclass = nullptr;
   auto residents = [&](KsimSweepCarver& cv, size_t) {
@@ -395,11 +411,17 @@ int sweep_general(Sweep& sw) {
       affd.raw = cv.take<int64_t>(C * N);
       residents(cv, C);
     }
+    if (sw.vol) {
+      vold.slots = cv.take<uint64_t>(C * VS * N);
+      vold.slot_count = cv.take<int32_t>(C * N);
+      vold.vol = cv.take<KsimVol>(C);
+    }
   };
   // chunk-independent: off the budget first
   const size_t b_rq = (rq ? ksim_sweep_measure(prefix, 0) : 0) + (ipa ? ksim_sweep_measure(residents, 0) : 0);
   const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + sw.MW() + why_bytes(sw.wcap) +
-                     (spr ? CL * 4 + sizeof(KsimAff) : 0) + (ipa ? KL * 8 + N * 8 : 0);
+                     (spr ? CL * 4 + sizeof(KsimAff) : 0) + (ipa ? KL * 8 + N * 8 : 0) +
+                     (sw.vol ? N * (8 * VS + 4) + sizeof(KsimVol) : 0);
   const int32_t chunk = sweep_scratch(sw, &h->sw_scratch, &h->sw_scratch_bytes, per, b_rq, layout);
   if (!chunk) return KSIM_E_NOMEM;
   a.n_pods = (int32_t)count;
@@ -430,6 +452,7 @@ int sweep_general(Sweep& sw) {
       HIPCHK(h, hipMemcpyAsync(rclass, sw.res->aff_class, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
     }
   }
+  if (sw.vol) vold.base = h->vol_h;  // every launch copies the handle's current mounts: its own are only read
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
   if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
@@ -438,8 +461,8 @@ int sweep_general(Sweep& sw) {
     const int32_t nsc = std::min(chunk, n_scen - s0);
     a.scen0 = s0;  // the chunk's first scenario: its row of the weights
     if (int rc = chunk_absent(sw, d, s0, nsc)) return rc;
-    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, spr ? &sprd : nullptr, ipa ? &affd : nullptr, nsc, d.absent,
-                                             sw.aw, derr, h->ev0, h->ev1, ksim_stream(h));
+    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, spr ? &sprd : nullptr, ipa ? &affd : nullptr, sw.vol ? &vold : nullptr,
+                                             nsc, d.absent, sw.aw, derr, h->ev0, h->ev1, ksim_stream(h));
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
     HIPCHK(h, hipEventSynchronize(h->ev1));
     float c_ms = 0.f;
@@ -455,6 +478,10 @@ int sweep_general(Sweep& sw) {
     return ksim_fail(h, KSIM_E_INVAL, "%s: scenario %d: a counted pair is negative once the residents of its absent nodes "
                                  "are taken out (the residents are not the placed pods behind the handle's counts)", who, bad);
   }
+  if (err && sw.vol)
+    return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's volume slots or host-port slots overflowed, or a mount count of a "
+                                    "volume saturated, in a scenario (load the volume tables with more vol_slots, or the "
+                                    "node table with more port slots)", who);
   if (err)
     return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's host-port slots overflowed in a scenario (load the node table with "
                                     "more port slots)", who);
@@ -700,6 +727,31 @@ int check_queue(ksim_handle* h, const char* who, int32_t n_scen, const ksim_swee
   return KSIM_OK;
 }
 
+// ksim_sweep_affinity, ksim_sweep_volumes: stale tables, and the residents against the loaded affinity
+// tables, before the device is touched
+int check_residents(ksim_handle* h, const char* who, const ksim_sweep_residents* res) {
+  if (h->have_aff && h->aff_stale)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the affinity tables predate a node event; load them again", who);
+  if (h->have_vol && h->vol_stale)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the volume tables predate a node event; load them again", who);
+  if (res && res->n < 0) return ksim_fail(h, KSIM_E_INVAL, "%s: a negative number of residents", who);
+  if (res && res->n > 0) {
+    if (!res->node || !res->aff_ident || !res->aff_class)
+      return ksim_fail(h, KSIM_E_INVAL, "%s: residents without a node, aff_ident or aff_class array", who);
+    // (without tables the call is refused below; the bounds are then the empty tables')
+    const int32_t ni = h->have_aff ? h->aff_n_ident : 0, na = h->have_aff ? h->aff_n_aclass : 0;
+    for (int64_t k = 0; k < res->n; ++k) {
+      if (res->node[k] < 0 || res->node[k] >= h->ctx.n)
+        return ksim_fail(h, KSIM_E_INVAL, "%s: resident %lld: node %d outside [0, %lld)", who, (long long)k, res->node[k],
+                    (long long)h->ctx.n);
+      if (res->aff_ident[k] < 0 || res->aff_ident[k] > ni || res->aff_class[k] < 0 || res->aff_class[k] > na)
+        return ksim_fail(h, KSIM_E_INVAL, "%s: resident %lld: identity %d or class %d beyond the loaded tables (%d, %d)", who,
+                    (long long)k, res->aff_ident[k], res->aff_class[k], ni, na);
+    }
+  }
+  return KSIM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,25 +797,7 @@ int ksim_sweep_affinity(ksim_handle* h, const uint32_t* absent, int32_t n_scen, 
   const char* who = "ksim_sweep_affinity";
   if (int rc = check_failures(h, who, fail)) return rc;
   if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
-  if (h->have_aff && h->aff_stale)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the affinity tables predate a node event; load them again", who);
-  if (h->have_vol && h->vol_stale)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the volume tables predate a node event; load them again", who);
-  if (res && res->n < 0) return ksim_fail(h, KSIM_E_INVAL, "%s: a negative number of residents", who);
-  if (res && res->n > 0) {
-    if (!res->node || !res->aff_ident || !res->aff_class)
-      return ksim_fail(h, KSIM_E_INVAL, "%s: residents without a node, aff_ident or aff_class array", who);
-    // (without tables the call is refused below; the bounds are then the empty tables')
-    const int32_t ni = h->have_aff ? h->aff_n_ident : 0, na = h->have_aff ? h->aff_n_aclass : 0;
-    for (int64_t k = 0; k < res->n; ++k) {
-      if (res->node[k] < 0 || res->node[k] >= h->ctx.n)
-        return ksim_fail(h, KSIM_E_INVAL, "%s: resident %lld: node %d outside [0, %lld)", who, (long long)k, res->node[k],
-                    (long long)h->ctx.n);
-      if (res->aff_ident[k] < 0 || res->aff_ident[k] > ni || res->aff_class[k] < 0 || res->aff_class[k] > na)
-        return ksim_fail(h, KSIM_E_INVAL, "%s: resident %lld: identity %d or class %d beyond the loaded tables (%d, %d)", who,
-                    (long long)k, res->aff_ident[k], res->aff_class[k], ni, na);
-    }
-  }
+  if (int rc = check_residents(h, who, res)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
   if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
@@ -771,6 +805,25 @@ int ksim_sweep_affinity(ksim_handle* h, const uint32_t* absent, int32_t n_scen, 
            rq ? out_rehosted : nullptr};
   sw.aw = (int32_t)((h->ctx.n + 31) / 32);
   sw.ipa = true;
+  sw.res = res;
+  return sweep_general(sw);
+}
+
+int ksim_sweep_volumes(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_residents* res,
+                       const ksim_sweep_requeue* rq, int64_t first, int64_t count, int32_t* out_node,
+                       uint64_t* out_counters, int32_t* out_scheduled, int32_t* out_rehosted,
+                       const ksim_sweep_failures* fail, ksim_stats* st) {
+  const char* who = "ksim_sweep_volumes";
+  if (int rc = check_failures(h, who, fail)) return rc;
+  if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
+  if (int rc = check_residents(h, who, res)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
+  if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
+  Sweep sw{h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
+           rq ? out_rehosted : nullptr};
+  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
+  sw.vol = true;
   sw.res = res;
   return sweep_general(sw);
 }

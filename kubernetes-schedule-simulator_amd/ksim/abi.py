@@ -276,6 +276,10 @@ def lib():
     L.ksim_sweep_affinity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepResidents),
                                       C.POINTER(SweepRequeue), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(Stats)]
+    # include/ksim_volsweep.h (likewise)
+    L.ksim_sweep_volumes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepResidents),
+                                     C.POINTER(SweepRequeue), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(Stats)]
     podargs = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     L.ksim_schedule_one.argtypes = [C.c_void_p] + podargs + [C.c_int32, C.POINTER(Result)]
     L.ksim_pod_add.argtypes = [C.c_void_p, C.c_int64] + podargs

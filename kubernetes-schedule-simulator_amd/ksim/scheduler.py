@@ -661,14 +661,36 @@ class GenericScheduler:
         (KsimUnsupported): no affinity tables, volumes on a swept pod, auxiliary or lender tables,
         more than abi.MAX_RCLASS reduce classes, more than abi.SWEEP_SPREAD_MAX_ZONES zones with
         SelectorSpread state, a node-sharded scheduler, more than abi.SWEEP_GENERAL_MAX_NODES nodes."""
+        return self._sweep_owned("sweep_affinity", "ksim_sweep_affinity", absent, requeue, first, count, explain, bound)
+
+    def sweep_volumes(self, absent, requeue=None, first=0, count=None, explain=None, bound=()):
+        """Outage and drain what-ifs over volume queues (ksim_sweep_volumes, include/ksim_volsweep.h):
+        sweep(None, absent=...) when requeue is None and sweep_drain(absent, requeue, ...) otherwise,
+        on a scheduler with volume tables, where range and re-queued pods may mount volumes.  Every
+        scenario starts from the scheduler's current mounts (as loaded, plus what an earlier schedule()
+        committed) in a copy of its own; NoDiskConflict, the MaxPD filters and NoVolumeZoneConflict run
+        at their places in the configured order, and a pod that binds adds its mounts to its node in
+        that copy.  The mounts of an absent node are never read.  With affinity tables the scenarios
+        run under SelectorSpread, MatchInterPodAffinity and InterPodAffinityPriority as in
+        sweep_affinity; bound matters only when those tables hold inter-pod affinity terms (the
+        residents, as there).  Returns, last_scheduled, last_rehosted and last_failures exactly as
+        sweep_affinity.  Always the general form.  KsimError E_OVERFLOW: a scenario's commit found a
+        node's volume slots full (the scheduler's own mounts are untouched).  Refused
+        (KsimUnsupported): no volume tables, auxiliary or lender tables, more than abi.MAX_RCLASS
+        reduce classes, more than abi.SWEEP_SPREAD_MAX_ZONES zones with SelectorSpread state, a
+        node-sharded scheduler, more than abi.SWEEP_GENERAL_MAX_NODES nodes."""
+        return self._sweep_owned("sweep_volumes", "ksim_sweep_volumes", absent, requeue, first, count, explain, bound)
+
+    def _sweep_owned(self, who, entry, absent, requeue, first, count, explain, bound):
+        """sweep_affinity / sweep_volumes: the entries whose scenarios own affinity or volume state."""
         n = len(self._pods)
         count = n - first if count is None else count
         mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
         if requeue is None and mask is None:
-            raise abi.KsimError(abi.E_INVAL, "sweep_affinity: neither absent sets nor re-queue lists")
+            raise abi.KsimError(abi.E_INVAL, "%s: neither absent sets nor re-queue lists" % who)
         S = len(requeue) if requeue is not None else len(mask)
         if mask is not None and len(mask) != S:
-            raise abi.KsimError(abi.E_INVAL, "sweep_affinity: %d re-queue lists but %d absent sets" % (S, len(mask)))
+            raise abi.KsimError(abi.E_INVAL, "%s: %d re-queue lists but %d absent sets" % (who, S, len(mask)))
         res = [np.asarray(self.cluster.residents, np.int32).reshape(-1, 3)]
         for q, w in bound:
             p = self._pods[int(q)]
@@ -699,7 +721,7 @@ class GenericScheduler:
             f = C.byref(abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
                                           abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32)))
         st = abi.Stats()
-        self.h.call("ksim_sweep_affinity", abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out), abi.vptr(ctr),
+        self.h.call(entry, abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out), abi.vptr(ctr),
                     abi.vptr(sched), abi.vptr(rehosted), f, C.byref(st))
         self.last_stats = st
         self.last_scheduled = sched
@@ -1064,7 +1086,11 @@ class ClusterCapacity:
         affinity terms (required, preferred, or carried by a running pod) is swept through
         GenericScheduler.sweep_affinity: every outage evaluates MatchInterPodAffinity and
         InterPodAffinityPriority on its own counts, without the running pods of its lost nodes.
-        Queues with volume state are refused (KsimUnsupported), as by GenericScheduler.sweep.
+        A snapshot with volume state (pods with EBS, GCE PD, Azure disk or PVC volumes under a volume
+        predicate; pvs= / pvcs= listers) is swept through GenericScheduler.sweep_volumes: every outage
+        evaluates NoDiskConflict, the MaxPD filters and NoVolumeZoneConflict on its own mounts, which
+        its binds extend; the mounts of a lost node go with it.  check_volume_support still refuses
+        what the reference errs on.
         Returns one record per outage: dict(name, absent (node count), scheduled, failed,
         placements [(pod name, node name or None)] in queue order).
         explain (ksim_sweep_explain): True, or an int cap per outage — each record gains listed (the
@@ -1089,7 +1115,9 @@ class ClusterCapacity:
         predicates, priorities, kw = self._sched_args
         g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
         try:
-            if g.has_affinity_terms():  # inter-pod affinity terms: every outage owns its affinity state
+            if g.volumes is not None:  # volume tables: every outage owns its mounts (and its affinity state)
+                out, _, _ = g.sweep_volumes(sets_, None, first, count, explain=explain if explain else None)
+            elif g.has_affinity_terms():  # inter-pod affinity terms: every outage owns its affinity state
                 out, _, _ = g.sweep_affinity(sets_, None, first, count, explain=explain if explain else None)
             else:
                 out, _, _ = g.sweep(None, first, count, absent=sets_, explain=explain if explain else None)
@@ -1126,8 +1154,9 @@ class ClusterCapacity:
         built with the constructor's listers and policy — and on a scheduler of its own.  With spread=
         listers the evicted pods of a service or controller are re-hosted under the spread priority, as
         the queue is, and with inter-pod affinity terms in the snapshot both are swept through
-        GenericScheduler.sweep_affinity, as in what_if.  Queues and evicted pods with volume state are
-        refused (KsimUnsupported).
+        GenericScheduler.sweep_affinity, as in what_if.  With volume state in the snapshot both are swept
+        through GenericScheduler.sweep_volumes: an evicted pod carries its disks to the survivor that
+        takes it, where they count for MaxPD and NoDiskConflict against the pods after it.
         first / count select the queue's range as in what_if (count=0: only re-host).
         Returns one record per outage: dict(name, absent (node count), evicted, rehosted, stranded,
         requeued [(pod name, node name or None)] in eviction order, scheduled, failed, placements
@@ -1164,7 +1193,8 @@ class ClusterCapacity:
         predicates, priorities, kw = self._sched_args
         g = GenericScheduler(dcl, predicates, priorities, collect_reasons=False, **kw)
         try:
-            drain = g.sweep_affinity if g.has_affinity_terms() else g.sweep_drain
+            drain = (g.sweep_volumes if g.volumes is not None else
+                     g.sweep_affinity if g.has_affinity_terms() else g.sweep_drain)
             out, pre, _, _ = drain(sets_, requeue, first, count, explain=explain if explain else None)
             fails = g.last_failures if explain else None
         finally:
