@@ -795,7 +795,15 @@ int ksim_schedule_one(ksim_handle* h, const ksim_pod* pod, const uint64_t* ports
   // every scratch buffer the launch forms read is allocated (or re-allocated) BEFORE the per-pod
   // context is copied from the handle's, so the copy never holds a freed or null pointer (round 4:
   // an illegal access when the wide decision's wmx / wcnt were re-allocated after the copy)
-  const int npt = ksim_rt_pick_npt(c.n);
+  int npt = ksim_rt_pick_npt(c.n);
+  // KSIM_PICK_NPT=2|4|8 (tests, read per call): nodes per thread of this call's pick, resident and
+  // scan launches, whose NPT 2 / 4 / 8 instantiations the table sizes of the pick forms never reach
+  // by themselves.  Ignored when it is no such value or its grid would exceed 1,024 blocks; the
+  // batch forms do not read it.
+  if (const char* kn = getenv("KSIM_PICK_NPT")) {
+    const int v = (kn[0] == '2' || kn[0] == '4' || kn[0] == '8') && kn[1] == 0 ? kn[0] - '0' : 0;  // exactly "2", "4" or "8"
+    if (v && (c.n + (int64_t)KSIM_BLOCK * v - 1) / ((int64_t)KSIM_BLOCK * v) <= 1024) npt = v;
+  }
   const int grid = (int)((c.n + (int64_t)KSIM_BLOCK * npt - 1) / ((int64_t)KSIM_BLOCK * npt));
   if ((rc = ksim_rt_ensure_partials(h, grid))) return rc;
   KsimCtx cs;
@@ -954,9 +962,10 @@ int ksim_schedule_one(ksim_handle* h, const ksim_pod* pod, const uint64_t* ports
   cs.fuse_a = 0;
   if (ipa && !h->fuse_off) {
     const char* fz = getenv("KSIM_FUSE_A");
-    if (h->one_fuse_grid != grid) {
+    const int fuse_key = grid * 16 + npt;  // (the co-residency is the instantiation's: NPT is part of it)
+    if (h->one_fuse_key != fuse_key) {
       h->one_fuse_ok = !(fz && fz[0] == '0') && ksim_scan_coresident(npt, 1, grid);
-      h->one_fuse_grid = grid;
+      h->one_fuse_key = fuse_key;
     }
     cs.fuse_a = h->one_fuse_ok ? 1 : 0;
   }

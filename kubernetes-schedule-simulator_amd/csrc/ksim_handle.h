@@ -259,7 +259,7 @@ struct ksim_handle {
   char* pg_rec = nullptr;                  // pod-context records of the current call
   size_t pg_rec_bytes = 0;
   bool fuse_off = false;        // a fused pass-A barrier timed out once: pass A as its own launch
-  int one_fuse_grid = -1;       // ksim_schedule_one: the grid whose co-residency was checked ...
+  int one_fuse_key = -1;       // ksim_schedule_one: the grid * 16 + NPT whose co-residency was checked ...
   bool one_fuse_ok = false;     // ... and whether the fused pass A may run on it
   bool pgen_off = false;        // a general persistent kernel ran out of a spin bound once: the launch form
   std::vector<void*> aff_bufs;
