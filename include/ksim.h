@@ -653,11 +653,15 @@ int ksim_set_counter(ksim_handle* h, uint64_t value);
 
 /* Form of the dominant kernel of the last ksim_schedule call (diagnostic, handle state only):
  * KSIM_FORM_FAST = the specialised resource-only persistent kernel, with KSIM_FORM_STREAM when its
- * rows streamed from HBM and KSIM_FORM_CACHED when it kept per-class evaluations in LDS; bits 8-15
- * hold its rows per row thread (1, 2, 4 or 9).  0 for every other kernel and before any call. */
+ * rows streamed from HBM and KSIM_FORM_CACHED when it kept per-class evaluations in LDS, and
+ * KSIM_FORM_HIST (always with KSIM_FORM_FAST | KSIM_FORM_CACHED) when it also kept per-class score
+ * histograms and took each pod's statistics from them (every score at most 63, the counts fit
+ * LDS; KSIM_NO_PHIST=1 disables it); bits 8-15 hold its rows per row thread (1, 2, 4 or 9).
+ * 0 for every other kernel and before any call. */
 #define KSIM_FORM_FAST 1
 #define KSIM_FORM_STREAM 2
 #define KSIM_FORM_CACHED 4
+#define KSIM_FORM_HIST 8
 #define KSIM_FORM_ROWS_SHIFT 8
 int ksim_last_form(ksim_handle* h, int32_t* form);
 

@@ -55,10 +55,11 @@ extern "C" size_t ksim_pfast_granule_bytes(void);
 extern "C" size_t ksim_shard_xchg_bytes(void);
 extern "C" size_t ksim_shard_lx_offset(void);
 extern "C" size_t ksim_pfast_cache_bytes(int lds_rows, int ncls);
+extern "C" size_t ksim_pfast_hist_bytes(int lds_rows, int ncls);
 extern "C" int ksim_pfast_rows_per_thread(int lds_rows, int stream);
 extern "C" hipError_t ksim_launch_pfast(const KsimCtx* c, uint64_t* granules, int grid, int lds_rows, double* mirror,
                                         const KsimShard* sh, const int32_t* tcls, const KsimTreeClass* tclass, int ncls,
-                                        hipStream_t s);
+                                        int hist, hipStream_t s);
 extern "C" hipError_t ksim_tree_build(const KsimCtx* c, const KsimTreeGeo* g, const KsimTreeClass* cls,
                                       const int32_t* tcls, int32_t* leaves, uint64_t* levels, int32_t* fitc,
                                       double* ty, const KsimTreeSweep* sw, hipStream_t s);

@@ -27,11 +27,19 @@
 //    post-commit one with scalar arithmetic, publishes, and only then commits the row;
 //  * one prefix scan per decision: counts at the maximum give C (= its total) and the
 //    workgroup holding the ix-th match from the top (core/generic_scheduler.go:183-198).
+//
+// Cached form (CACHE): every (tree class, row) evaluation stays in LDS and only the committed
+// row is re-evaluated.  Its histogram sub-form (HIST, scores <= 63): per class the number of
+// rows at each score (ksim_phist.h), so a pod's (fit count, maximum, count at the maximum) is
+// one histogram row read lane = score instead of a scan of the class's column, the owner's
+// fix is that row with two buckets adjusted, and what the owner needs of pod + 1 is read
+// before the sweep and the first barrier.  The exchange itself is the same in every form.
 #include <algorithm>
 
 #include "ksim_decide.h"
 #include "ksim_f64.h"
 #include "ksim_fast.h"
+#include "ksim_phist.h"
 #include "ksim_tree.h"
 #include "ksim_wave.h"
 #include "ksim_xchg.h"
@@ -180,6 +188,7 @@ struct FRows {  // LDS image of the owned rows (SoA)
   uint32_t* rm2;  // [chunk]: ... its reason mask
   uint32_t* rma;  // STREAM: [2][chunk] reason mask of ev (registers in the LDS form)
   int16_t* cache; // CACHE: [ncls][chunk] evaluation of tree class k on row j as it stands
+  uint16_t* hist; // HIST: [ncls][64] rows of the workgroup at each score of class k (ksim_phist.h)
 };
 
 constexpr int LDS_ROW_BYTES = 8 * 8 + 8 * 4;  // 96: 8 float64 + allowed, count, flags, ev[2], ev2, rm2, top_list
@@ -206,6 +215,7 @@ __device__ __forceinline__ FRows carve(int rows, const PfArgs& a, int64_t lo) {
     r.rm2 = reinterpret_cast<uint32_t*>(q + 3 * rows);
     r.rma = r.rm2 + 2 * rows;  // after top_list
     r.cache = nullptr;
+    r.hist = nullptr;
     return r;
   }
   double* d = reinterpret_cast<double*>(kf_smem);
@@ -218,6 +228,7 @@ __device__ __forceinline__ FRows carve(int rows, const PfArgs& a, int64_t lo) {
   r.ev2 = q + 5 * rows;
   r.rm2 = reinterpret_cast<uint32_t*>(q + 6 * rows);
   r.cache = reinterpret_cast<int16_t*>(q + 8 * rows);  // after top_list (q + 7 rows)
+  r.hist = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(r.cache) + (((size_t)a.ncls * rows * 2 + 15) & ~(size_t)15));
   return r;
 }
 
@@ -265,10 +276,11 @@ struct Top2 {
 
 }  // namespace
 
-template <int NPT, bool STREAM, bool CACHE>
+template <int NPT, bool STREAM, bool CACHE, bool HIST = false>
 __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
   static_assert(!(STREAM && CACHE), "the cached form keeps the rows in LDS");
-  __shared__ int32_t s_wst[2][RW][5];         // per row wave: fit, m1, c1, m2, c2 (by pod parity)
+  static_assert(!HIST || CACHE, "the histograms count the cached evaluations");
+  __shared__ int32_t s_wst[HIST ? 1 : 2][HIST ? 1 : RW][5];  // per row wave: fit, m1, c1, m2, c2 (by pod parity)
   __shared__ uint64_t s_bm[2][NPT][RW];       // per 64-row segment: rows at the wave maximum
   __shared__ int32_t s_wg[2][5];              // workgroup top-two of the pod
   __shared__ int32_t s_fix[2][2];             // {row the owner corrected (-1 none), its reason mask}
@@ -349,10 +361,17 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
   };
   if (CACHE) {  // every (class, owned row) evaluation, once per call
     const int tot = a.ncls * nrows;
+    uint32_t* const hw = reinterpret_cast<uint32_t*>(R.hist);  // HIST: two counts a word (ksim_phist.h)
+    if (HIST) {
+      for (int i = tid; i < a.ncls * (KSIM_PHIST_BUCKETS / 2); i += BS) hw[i] = 0;
+      __syncthreads();
+    }
     for (int idx = tid; idx < tot; idx += BS) {
       const int k = idx / nrows, j = idx - k * nrows;
       uint32_t rm;
-      R.cache[k * chunk + j] = (int16_t)feval(EC, cls_fpod(k), load_frow<false>(R, j), rm);
+      const int32_t ev = feval(EC, cls_fpod(k), load_frow<false>(R, j), rm);
+      R.cache[k * chunk + j] = (int16_t)ev;
+      if (HIST && ev >= 0) atomicAdd(&hw[k * (KSIM_PHIST_BUCKETS / 2) + khist::word(ev)], khist::unit(ev));
     }
     __syncthreads();
   }
@@ -413,6 +432,32 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         ksimx::store_agent((gu64*)spec_at(granules + lane * REP_STRIDE, (int)(p % NSLOT), me), gpack(ptag(p), t.f, t.c1, t.m1));
     }
   };
+  // HIST, row waves: pod p's statistics are its class's histogram row (lane = score): F its sum,
+  // M its highest non-empty bucket, C that bucket.  Wave 1 publishes them (the stores of
+  // arrive_publish); every wave then leaves the masks of its rows at M — the workgroup's
+  // maximum, not the wave's — for seg_prepare.  No wave waits for another.
+  auto hist_publish = [&](int64_t p, int buf) {
+    const int cls = s_pcls[p % RING];
+    const int32_t h = R.hist[cls * KSIM_PHIST_BUCKETS + lane];
+    const int32_t M = khist::top(__ballot(h != 0));
+    if (wv == 1) {
+      const int32_t F = ksimw::sum_i32(h);
+      const int32_t C = __builtin_amdgcn_readlane(h, M < 0 ? 0 : M);  // (an empty row: bucket 0 holds 0)
+      if (lane == 0) {
+        s_wg[buf][0] = F; s_wg[buf][1] = M; s_wg[buf][2] = C;
+        if (NR == 1) ksimx::store_agent((gu64*)spec_at(granules, (int)(p % NSLOT), me), gpack(ptag(p), F, C, M));
+      }
+      if (NR > 1 && lane < NR)
+        ksimx::store_agent((gu64*)spec_at(granules + lane * REP_STRIDE, (int)(p % NSLOT), me), gpack(ptag(p), F, C, M));
+    }
+    const int16_t* c1 = R.cache + cls * chunk;
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+      const int32_t j = k * RT + rt;
+      const uint64_t bm = __ballot(M >= 0 && j < nrows && (int32_t)c1[j] == M);
+      if (lane == 0) s_bm[buf][k][wv - 1] = bm;
+    }
+  };
   // LDS form, control wave: the 64-row segments holding rows at the workgroup maximum of the pod in `buf`
   // (lane t = t-th segment from the top: its bitmask, count, and the matches in segments above
   // it), read before the sweep; the owner turns its rank into a row with a few wave operations
@@ -427,7 +472,8 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
     sg.m = 0;
     if (lane < S) {
       const int k = NPT - 1 - lane / RW, w = RW - 1 - lane % RW;
-      sg.m = (M >= 0 && s_wst[buf][w][1] == M) ? s_bm[buf][k][w] : 0ull;
+      if constexpr (HIST) sg.m = M >= 0 ? s_bm[buf][k][w] : 0ull;  // already against the workgroup's maximum
+      else sg.m = (M >= 0 && s_wst[buf][w][1] == M) ? s_bm[buf][k][w] : 0ull;
     }
     sg.cnt = __popcll(sg.m);
     const int32_t incl = ksimw::prefix_incl_i32(sg.cnt);
@@ -497,8 +543,12 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         ev[j] = e[k];
       }
     }
-    wave_stats(e, (int)(a.first & 1), wv);
-    arrive_publish(a.first, (int)(a.first & 1));
+    if constexpr (HIST) {
+      hist_publish(a.first, (int)(a.first & 1));
+    } else {
+      wave_stats(e, (int)(a.first & 1), wv);
+      arrive_publish(a.first, (int)(a.first & 1));
+    }
   }
   int X = -1;  // control wave: owner workgroup of the previous pod's node (-1: none)
   int64_t stop_at = a.end;  // first pod not scheduled by this call
@@ -519,6 +569,10 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
     FRow jrow;              // STREAM: that row as loaded by the owner
     int32_t e_new = -1;     // STREAM: pod + 1 against the row after pod's commit
     uint32_t m_new = 0;
+    int32_t hM_old = -1, hM_new = -1;  // HIST, owner: the workgroup's maximum of pod + 1 before / after the fix
+    int32_t hcls = 0, hrow = 0, hF0 = 0;  // HIST, control wave: pod + 1's class, its histogram row (lane = score), its F
+    int32_t he_old = -1;                  // HIST, owner: the committed row's cached evaluation for that class
+    double hdel[4] = {0.0, 0.0, 0.0, 0.0};  // HIST, control wave: pod's AddPod deltas
 #ifdef KSIM_STAMPS
     uint64_t o_prev = 0;
 #endif
@@ -527,6 +581,18 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       Segs sg{};
       if (STREAM) build_top_list(pb);
       else sg = seg_prepare(pb);
+      if constexpr (HIST) {
+        // what an owner needs of pod + 1 and of pod's deltas, read while the sweep waits anyway:
+        // the class's histogram row (nothing moves a count before the owner's fix) and its F and M
+        if (has_next) {
+          hcls = s_pcls[(pod + 1) % RING];
+          hrow = R.hist[hcls * KSIM_PHIST_BUCKETS + lane];
+          hF0 = ksimw::sum_i32(hrow);
+          hM_old = khist::top(__ballot(hrow != 0));
+        }
+        const ksim_pod& Pp = s_pod[pod % RING];
+        hdel[0] = (double)Pp.add_cpu; hdel[1] = (double)Pp.add_mem; hdel[2] = (double)Pp.nz_cpu; hdel[3] = (double)Pp.nz_mem;
+      }
       STAMP(1);
       // ---------------- a. sweep: every workgroup's granule of pod (+ the owner's fix) -------
       const uint64_t tag = ptag(pod);
@@ -650,6 +716,12 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           jsel = -1;
           mode = -1;
           if (lane == 0) atomicOr(a.err, 2);
+        } else if (HIST) {
+          // the four sums at once (no short-circuit: one round of LDS reads), the deltas converted
+          // before the sweep; and the row's evaluation for pod + 1's class, which no row wave writes
+          const double s0 = R.rc[jsel] + hdel[0], s1 = R.rm[jsel] + hdel[1], s2 = R.zc[jsel] + hdel[2], s3 = R.zm[jsel] + hdel[3];
+          if (has_next) he_old = (int32_t)R.cache[hcls * chunk + jsel];
+          stopbit = ((s0 >= EXACT_LIM) | (s1 >= EXACT_LIM) | (s2 >= EXACT_LIM) | (s3 >= EXACT_LIM)) ? (1ull << 55) : 0ull;
         } else if (!STREAM) {
           const ksim_pod& Pp = s_pod[pod % RING];
           stopbit = (R.rc[jsel] + (double)Pp.add_cpu >= EXACT_LIM || R.rm[jsel] + (double)Pp.add_mem >= EXACT_LIM ||
@@ -736,16 +808,24 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         // cached form: pod + 1's statistics are its class's cached evaluations (the rows as they
         // stand), then pod + 1 against "row + pod" only for the rows pod can commit to — the
         // rows at this workgroup's maximum of pod (its owner picks one of them)
-        const int16_t* c1 = R.cache + s_pcls[(pod + 1) % RING] * chunk;
+        if constexpr (HIST) {
+          // histogram sub-form: the statistics come from the class's score histogram, which only
+          // a commit to this workgroup changes — no scan of the column, no merge across waves
+          WSTAMP(9);
+          hist_publish(pod + 1, nb);
+          WSTAMP(10);
+        } else {
+          const int16_t* c1 = R.cache + s_pcls[(pod + 1) % RING] * chunk;
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-          const int32_t j = k * RT + rt;
-          e[k] = j < nrows ? (int32_t)c1[j] : -1;
+          for (int k = 0; k < NPT; ++k) {
+            const int32_t j = k * RT + rt;
+            e[k] = j < nrows ? (int32_t)c1[j] : -1;
+          }
+          WSTAMP(9);
+          wave_stats(e, nb, wv);
+          WSTAMP(10);
+          arrive_publish(pod + 1, nb);
         }
-        WSTAMP(9);
-        wave_stats(e, nb, wv);
-        WSTAMP(10);
-        arrive_publish(pod + 1, nb);
         const int32_t M0 = s_wg[pb][1];
         const int16_t* c0 = R.cache + s_pcls[pod % RING] * chunk;
 #pragma unroll
@@ -838,14 +918,32 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           if (!STREAM) { e_new = R.ev2[jsel]; m_new = R.rm2[jsel]; }
           // the workgroup's pod + 1 statistics without the committed row's pre-commit
           // evaluation, with its post-commit one (straight-line selects)
-          const int32_t e_old = CACHE ? (int32_t)R.cache[s_pcls[(pod + 1) % RING] * chunk + jsel] : R.ev[nb * chunk + jsel];
-          const int32_t f0 = s_wg[nb][0], m1 = s_wg[nb][1], c1 = s_wg[nb][2], m2 = s_wg[nb][3], c2 = s_wg[nb][4];
+          int32_t e_old, f0, m1 = -1, c1 = 0, m2 = -1, c2 = 0;
+          if constexpr (HIST) {  // read before the barrier: only e_new waited for the row waves
+            e_old = he_old;
+            f0 = hF0;
+          } else {
+            e_old = CACHE ? (int32_t)R.cache[s_pcls[(pod + 1) % RING] * chunk + jsel] : R.ev[nb * chunk + jsel];
+            f0 = s_wg[nb][0]; m1 = s_wg[nb][1]; c1 = s_wg[nb][2]; m2 = s_wg[nb][3]; c2 = s_wg[nb][4];
+          }
           const bool rem = e_old >= 0, add = e_new >= 0;
-          const int32_t c1a = c1 - ((rem && e_old == m1) ? 1 : 0);
-          const int32_t mb = c1a ? m1 : (c2 ? m2 : -1), cb = c1a ? c1a : c2;
-          const bool up = add && (cb == 0 || e_new > mb), eq = add && !up && e_new == mb;
-          const int32_t M = up ? e_new : mb, Cn = up ? 1 : cb + (eq ? 1 : 0);
           const int32_t Ff = f0 - (rem ? 1 : 0) + (add ? 1 : 0);
+          int32_t M, Cn;
+          if constexpr (HIST) {
+            // the class's histogram row with the committed row moved from e_old to e_new in
+            // registers (lane = score): exact, whatever the buckets below the top hold.  (F moves
+            // by the same row: hF0 is the sum of the row as read.)
+            const int32_t h = khist::adjusted(hrow, lane, e_old, e_new);
+            M = khist::top(__ballot(h != 0));
+            Cn = __builtin_amdgcn_readlane(h, M < 0 ? 0 : M);
+            hM_new = M;
+          } else {
+            const int32_t c1a = c1 - ((rem && e_old == m1) ? 1 : 0);
+            const int32_t mb = c1a ? m1 : (c2 ? m2 : -1), cb = c1a ? c1a : c2;
+            const bool up = add && (cb == 0 || e_new > mb), eq = add && !up && e_new == mb;
+            M = up ? e_new : mb;
+            Cn = up ? 1 : cb + (eq ? 1 : 0);
+          }
           PROBE(2);
           if (NR > 1 && lane < NR)
             ksimx::store_agent((gu64*)fix_at(granules + lane * REP_STRIDE, (int)((pod + 1) % NSLOT)),
@@ -859,11 +957,14 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         OSTAMP(18);
         if (CACHE) {
           // the committed row's evaluation for every class (lane k = class k), off the critical
-          // path: the next pods' statistics read them after the barrier below
+          // path: the next pods' statistics read them after the barrier below; HIST: one count
+          // moves per class with it
           const FRow r2 = plus(load_frow<false>(R, jsel), load_fpod(s_pod[pod % RING]));
           if (lane < a.ncls) {
             uint32_t rm;
-            R.cache[lane * chunk + jsel] = (int16_t)feval(EC, cls_fpod(lane), r2, rm);
+            const int32_t en = feval(EC, cls_fpod(lane), r2, rm);
+            if constexpr (HIST) khist::move(R.hist + lane * KSIM_PHIST_BUCKETS, (int32_t)R.cache[lane * chunk + jsel], en);
+            R.cache[lane * chunk + jsel] = (int16_t)en;
           }
         }
         if (lane == 0) {  // commit: NodeInfo.AddPod into the LDS row (STREAM: deferred, s_prow)
@@ -885,7 +986,30 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         }
       }
       lds_barrier();  // uniform (own is workgroup-wide): row waves see the commit
-      if (wv == 0 && has_next) {
+      if (HIST && wv == 0 && has_next) {
+        // off the critical path: pod + 1's masks must be the rows at the corrected maximum.  It
+        // did not move: only the committed row's bit can differ.  It moved: every segment again,
+        // from the class's column (the committed row's entry is already the new evaluation).
+        if (hM_new == hM_old) {
+          if (lane == 0 && hM_new >= 0) {
+            uint64_t& m = s_bm[nb][jsel / RT][(jsel % RT) / 64];
+            const uint64_t bit = 1ull << (jsel & 63);  // RT is a multiple of 64
+            m = e_new == hM_new ? (m | bit) : (m & ~bit);
+          }
+        } else {
+          const int16_t* c1 = R.cache + s_pcls[(pod + 1) % RING] * chunk;
+          for (int sgi = 0; sgi < NPT * RW; ++sgi) {
+            const int32_t j = sgi * 64 + lane;  // segment (k, w) = (sgi / RW, sgi % RW): rows k * RT + w * 64 + lane
+            const uint64_t bm = __ballot(hM_new >= 0 && j < nrows && (int32_t)c1[j] == hM_new);
+            if (lane == 0) s_bm[nb][sgi / RW][sgi % RW] = bm;
+          }
+        }
+        OSTAMP(19);
+#ifdef KSIM_STAMPS
+        if (lane == 0) atomicAdd((unsigned long long*)&a.dbg[21], 1ull);
+#endif
+      }
+      if (!HIST && wv == 0 && has_next) {
         // off the critical path: the corrected wave's statistics and bitmasks
         const int w = 1 + (jsel % RT) / 64;
         int32_t e[NPT];
@@ -1040,6 +1164,17 @@ extern "C" size_t ksim_pfast_cache_bytes(int lds_rows, int ncls) {
   return (size_t)lds_rows * LDS_ROW_BYTES + b <= (size_t)PF_LDS_BUDGET ? b : 0;
 }
 
+// LDS bytes of the histogram sub-form's counts ([ncls][64] uint16, after the cached evaluations), 0
+// when the cached form does not apply or the counts do not fit beside the rows and the cache; the
+// sub-form needs every score below KSIM_PHIST_BUCKETS (host-checked).  ksim_pfast_cache_bytes'
+// answer — the cached / uncached boundary — does not depend on it.
+extern "C" size_t ksim_pfast_hist_bytes(int lds_rows, int ncls) {
+  const size_t cb = ksim_pfast_cache_bytes(lds_rows, ncls);
+  if (!cb) return 0;
+  const size_t hb = (size_t)ncls * KSIM_PHIST_BUCKETS * sizeof(uint16_t);
+  return (size_t)lds_rows * LDS_ROW_BYTES + cb + hb <= (size_t)PF_LDS_BUDGET ? hb : 0;
+}
+
 // rows per row thread of the instantiation ksim_launch_pfast picks (the same thresholds)
 extern "C" int ksim_pfast_rows_per_thread(int lds_rows, int stream) {
   return lds_rows <= RT ? 1 : lds_rows <= 2 * RT ? 2 : (lds_rows <= 4 * RT || !stream) ? 4 : 9;
@@ -1047,7 +1182,7 @@ extern "C" int ksim_pfast_rows_per_thread(int lds_rows, int stream) {
 
 extern "C" hipError_t ksim_launch_pfast(const KsimCtx* c, uint64_t* granules, int grid, int lds_rows, double* mirror,
                                         const KsimShard* sh, const int32_t* tcls, const KsimTreeClass* tclass, int ncls,
-                                        hipStream_t s) {
+                                        int hist, hipStream_t s) {
   PfArgs a;
   a.tcls = tcls; a.tclass = tclass; a.ncls = ncls;
   a.rank = sh->rank; a.world = sh->world; a.node_base = sh->node_base; a.xtag_base = sh->xtag_base;
@@ -1081,7 +1216,22 @@ extern "C" hipError_t ksim_launch_pfast(const KsimCtx* c, uint64_t* granules, in
   }
   const size_t cb = ncls > 0 ? ksim_pfast_cache_bytes(lds_rows, ncls) : 0;
   if (ncls > 0 && !cb) return hipErrorInvalidValue;
-  const size_t lds = (size_t)lds_rows * LDS_ROW_BYTES + cb;
+  const size_t hb = hist ? ksim_pfast_hist_bytes(lds_rows, ncls) : 0;
+  if (hist && !hb) return hipErrorInvalidValue;
+  const size_t lds = (size_t)lds_rows * LDS_ROW_BYTES + cb + hb;
+  if (hb) {  // histogram sub-form of the cached form
+#define KSIM_PFH(R, L)                                                                         \
+  do {                                                                                         \
+    hipError_t e_ = ksim_check_coresident(ksim_pfast_kernel<R, false, true, true>, grid, BS, L); \
+    if (e_ != hipSuccess) return e_;                                                           \
+    hipLaunchKernelGGL((ksim_pfast_kernel<R, false, true, true>), dim3(grid), dim3(BS), L, s, a); \
+  } while (0)
+    if (lds_rows <= RT) KSIM_PFH(1, lds);
+    else if (lds_rows <= 2 * RT) KSIM_PFH(2, lds);
+    else KSIM_PFH(4, lds);
+#undef KSIM_PFH
+    return hipGetLastError();
+  }
   if (cb) {  // cached form
     if (lds_rows <= RT) KSIM_PFC(1, false, true, lds);
     else if (lds_rows <= 2 * RT) KSIM_PFC(2, false, true, lds);

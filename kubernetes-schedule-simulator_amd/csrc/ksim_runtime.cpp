@@ -790,19 +790,23 @@ static int run_pfast_mode(ksim_handle* h, int64_t first, int64_t count, int grid
   c.chunk = (c.n + grid - 1) / grid;
   // the cached form (every pod of the range has a tree class, <= 64 classes, the classes'
   // evaluations fit LDS beside the rows, map scores below 2^15): KSIM_NO_PCACHE=1 disables it
-  int ncls = 0;
+  // Its histogram sub-form (every score at most 63, one lane per score, and the per-class score
+  // counts fit LDS as well): KSIM_NO_PHIST=1 disables it and leaves the cached form as it is.
+  int ncls = 0, hist = 0;
   if (!stream && !getenv("KSIM_NO_PCACHE") && h->n_tcls > 0 && h->tcls && h->tclass) {
     int64_t sw = 0;
     for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED}) sw += c.no_prio ? 0 : c.w[k] * 10;
     if (sw < 32767 && ksim_pfast_cache_bytes(lds_rows, h->n_tcls)) ncls = h->n_tcls;
+    if (ncls > 0 && sw <= 63 && !getenv("KSIM_NO_PHIST") && ksim_pfast_hist_bytes(lds_rows, ncls)) hist = 1;
   }
   h->last_pfast_cache = ncls > 0;
   h->last_form = KSIM_FORM_FAST | (stream ? KSIM_FORM_STREAM : 0) | (ncls > 0 ? KSIM_FORM_CACHED : 0) |
+                 (hist ? KSIM_FORM_HIST : 0) |
                  (ksim_pfast_rows_per_thread(lds_rows, stream ? 1 : 0) << KSIM_FORM_ROWS_SHIFT);
   HIPCHK(h, hipMemsetAsync(h->granules, 0, gb, ksim_stream(h)));
   HIPCHK(h, hipEventRecord(h->ev0, ksim_stream(h)));
   hipError_t e = ksim_launch_pfast(&c, h->granules, grid, lds_rows, stream ? h->mirror : nullptr, &h->shard, h->tcls,
-                                   h->tclass, ncls, ksim_stream(h));
+                                   h->tclass, ncls, hist, ksim_stream(h));
   if (e == hipErrorCooperativeLaunchTooLarge) {
     h->last_form = 0;
     // the grid cannot be co-resident here (a smaller or shared device): the general kernels instead

@@ -210,7 +210,7 @@ EXPORTS = ["ksim_abi_version", "ksim_last_error", "ksim_create", "ksim_destroy",
            "ksim_node_remove", "ksim_node_count", "ksim_append_pods", "ksim_load_affinity", "ksim_load_volumes",
            "ksim_read_volumes", "ksim_grow_volumes", "ksim_sweep_nodes", "ksim_last_form"]
 # ksim_last_form bits (include/ksim.h)
-FORM_FAST, FORM_STREAM, FORM_CACHED, FORM_ROWS_SHIFT = 1, 2, 4, 8
+FORM_FAST, FORM_STREAM, FORM_CACHED, FORM_HIST, FORM_ROWS_SHIFT = 1, 2, 4, 8, 8
 IPC_HANDLE_BYTES = 64
 MAX_RANKS = 8
 
