@@ -132,6 +132,14 @@ struct SwgVolumes {
   KsimVol* vol;         // [C]
 };
 
+// Policy sweeps (ksim_sweep_policy, include/ksim_polsweep.h, ksim_sweep_policy.hip): no instantiation
+// of their own.  The sweep kernels read all seven weights from the scenario's KsimCtx, so a policy
+// scenario is the handle's context with its whole weight row written over it
+// (ksim_sweep_policy_ctx_kernel, after the context kernel), under whichever plain, SPR, IPA or VOL
+// kernel the queue takes.  A scenario's outcome record on the device: listed, used, free_cpu[11],
+// free_mem[11] (ksim_sweep_outcome_kernel).
+#define KSIM_SWEEP_OUTCOME_WORDS 24
+
 // one uint32 evaluation per node in LDS, (map score << 4) | reduce class (150 KiB)
 #define KSIM_SWEEP_GENERAL_MAX_NODES 38400
 #define KSIM_SWEEP_GENERAL_SCORE_BITS 27  // 0xFFFFFFFF = does not fit stays above every packed word

@@ -869,9 +869,13 @@ extern "C" hipError_t ksim_sweep_general_vol_launch(const SwgArgsPre* args, cons
 // columns, the residents, and the word for the scenario whose corrected counts are negative.
 // vol set (alone, with spr, or with spr and ipa): the VOL instantiations (ksim_sweep_volumes): the
 // handle's volume descriptor and the chunk's mount copies and per-scenario descriptors.
+// polw set (ksim_sweep_policy; args->w is then null): the whole sweep's [S][KSIM_NW] weight rows, written
+// over the scenarios' contexts by ksim_sweep_policy.hip's kernel behind the context kernel.
+extern "C" hipError_t ksim_sweep_policy_ctx_launch(const int64_t* w, int32_t scen0, int32_t n_scen, KsimCtx* ctx,
+                                                   hipStream_t st);
 extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
                                                 const SwgSpread* spr, const SwgAffinity* ipa, const SwgVolumes* vol,
-                                                int32_t n_scen,
+                                                const int64_t* polw, int32_t n_scen,
                                                 const uint32_t* absent, int32_t absent_words, int32_t* err,
                                                 hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   const int64_t n = hc->n, total = n * (int64_t)n_scen;
@@ -897,6 +901,10 @@ extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols
   k.err = err;
   hipLaunchKernelGGL(ksim_sweep_general_ctx_kernel, dim3((unsigned)((n_scen + 63) / 64)), dim3(64), 0, st, k, args->w,
                      args->scen0, n_scen, args->ctx);
+  if (polw) {
+    e = ksim_sweep_policy_ctx_launch(polw, args->scen0, n_scen, args->ctx, st);
+    if (e != hipSuccess) return e;
+  }
   if (ipa) {
     const int64_t ct = ipa->carried_len * (int64_t)n_scen, thr = ct > n_scen ? ct : (int64_t)n_scen;
     hipLaunchKernelGGL(ksim_sweep_affinity_init_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st,

@@ -1,7 +1,7 @@
 // ksim_sweep_rt.cpp — host side of the scenario sweep: ksim_sweep (include/ksim.h),
 // ksim_sweep_nodes, ksim_sweep_explain (include/ksim_whatif.h), ksim_sweep_drain
-// (include/ksim_drain.h), ksim_sweep_affinity (include/ksim_affsweep.h) and ksim_sweep_volumes
-// (include/ksim_volsweep.h).
+// (include/ksim_drain.h), ksim_sweep_affinity (include/ksim_affsweep.h), ksim_sweep_volumes
+// (include/ksim_volsweep.h) and ksim_sweep_policy (include/ksim_polsweep.h).
 //
 // Three forms share one driver: the tree form (ksim_tree.hip) and the scan form (ksim_sweep_kernel)
 // for resource-only ranges, the general form (ksim_sweep_general_kernel) for every other.  A form
@@ -9,12 +9,19 @@
 // its launches; the chunk rule, the scratch (re)allocation, the weight checks, the per-chunk copies
 // and the statistics are written once, below.
 #include "ksim_handle.h"
+#include "ksim_polsweep_rules.h"
 #include "ksim_sweep_plan.h"
 
 #include "../../include/ksim_affsweep.h"
 #include "../../include/ksim_drain.h"
+#include "../../include/ksim_polsweep.h"
 #include "../../include/ksim_volsweep.h"
 #include "../../include/ksim_whatif.h"
+
+// ksim_sweep_policy.hip: a chunk's outcome records, [n_scen][KSIM_SWEEP_OUTCOME_WORDS], behind its sweep
+// kernel on the stream; ev1 is recorded again behind it
+extern "C" hipError_t ksim_sweep_outcome_launch(const KsimCtx* ctx, int32_t n_scen, int32_t* out, hipEvent_t ev1,
+                                                hipStream_t st);
 
 namespace {
 
@@ -47,6 +54,11 @@ struct Sweep {
   // ksim_sweep_volumes: range and prefix pods may mount volumes (the VOL instantiations), every scenario
   // on its own copy of the mounts; affinity terms in the tables are swept as by ksim_sweep_affinity
   bool vol = false;
+  // ksim_sweep_policy: weights holds whole rows, [n_scen][KSIM_NW], checked by the entry
+  // (ksim_policy_weight_rules); the queue takes whichever instantiation it would without weights, and
+  // outcome (may be null) receives every scenario's record
+  bool pol = false;
+  const ksim_sweep_outcome* outcome = nullptr;
 
   size_t S() const { return (size_t)n_scen; }
   size_t P() const { return (size_t)count; }
@@ -64,6 +76,7 @@ struct SweepOut {
   uint32_t* absent;
   int32_t *why_pod, *why_hist;
   int32_t* pre;
+  int32_t* outcome;  // [C][KSIM_SWEEP_OUTCOME_WORDS] (ksim_sweep_policy with outcome records)
 };
 
 SweepOut carve_out(KsimSweepCarver& cv, size_t C, const Sweep& sw) {
@@ -75,6 +88,7 @@ SweepOut carve_out(KsimSweepCarver& cv, size_t C, const Sweep& sw) {
     o.why_pod = cv.take<int32_t>(C * (size_t)sw.wcap);
     o.why_hist = cv.take<int32_t>(C * (size_t)sw.wcap * KSIM_NREASONS);
   }
+  if (sw.outcome) o.outcome = cv.take<int32_t>(C * KSIM_SWEEP_OUTCOME_WORDS);
   return o;
 }
 
@@ -219,6 +233,18 @@ int chunk_out(const Sweep& sw, const SweepOut& d, int32_t s0, int32_t nsc) {
   if (rq && rq->off[s0 + nsc] > rq->off[s0])
     HIPCHK(h, hipMemcpy(rq->out_node + rq->off[s0], d.pre + rq->off[s0], (size_t)(rq->off[s0 + nsc] - rq->off[s0]) * 4,
                         hipMemcpyDeviceToHost));
+  if (sw.outcome) {  // the chunk's records into the caller's four arrays
+    std::vector<int32_t> rec((size_t)nsc * KSIM_SWEEP_OUTCOME_WORDS);
+    HIPCHK(h, hipMemcpy(rec.data(), d.outcome, rec.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t s = 0; s < nsc; ++s) {
+      const int32_t* r = rec.data() + (size_t)s * KSIM_SWEEP_OUTCOME_WORDS;
+      sw.outcome->listed[s0 + s] = r[0];
+      sw.outcome->used[s0 + s] = r[1];
+      memcpy(sw.outcome->free_cpu + (size_t)(s0 + s) * KSIM_OUTCOME_BUCKETS, r + 2, KSIM_OUTCOME_BUCKETS * 4);
+      memcpy(sw.outcome->free_mem + (size_t)(s0 + s) * KSIM_OUTCOME_BUCKETS, r + 2 + KSIM_OUTCOME_BUCKETS,
+             KSIM_OUTCOME_BUCKETS * 4);
+    }
+  }
   return why_copy_out(sw, d, s0, nsc);
 }
 
@@ -289,7 +315,8 @@ int sweep_general(Sweep& sw) {
   // ksim_sweep_volumes (sw.vol) takes the IPA instantiations when the tables hold such terms, and else
   // the SPR or plain ones by the rule of every range; it needs the volume tables.
   const bool terms = h->have_aff && (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car);
-  const bool ipa = sw.ipa || (sw.vol && terms);
+  // ksim_sweep_policy (sw.pol) chooses as ksim_sweep_volumes does, with sw.vol = volume tables are loaded.
+  const bool ipa = sw.ipa || ((sw.vol || sw.pol) && terms);
   if (sw.vol && !h->have_vol)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: no volume tables are loaded (ksim_sweep_nodes, ksim_sweep_drain and "
                                        "ksim_sweep_affinity sweep such a queue)", who);
@@ -338,13 +365,13 @@ int sweep_general(Sweep& sw) {
                     (long long)q, KSIM_MAX_RCLASS);
     }
   }
-  if (sw.weights && (c.w[KSIM_W_TAINT_TOLERATION] || c.w[KSIM_W_NODE_AFFINITY] || c.use_na))
+  if (sw.weights && !sw.pol && (c.w[KSIM_W_TAINT_TOLERATION] || c.w[KSIM_W_NODE_AFFINITY] || c.use_na))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over pods that are not resource-only would drop the "
                                        "handle's reduce priorities or NodePreferAvoidPods addend (weights = NULL sweeps "
                                        "under the whole configured policy)", who);
   // the spread weight a spread pod's packed score carries beside the map weights
   const int64_t wspr = (spr && !c.no_prio) ? c.w[KSIM_W_SELECTOR_SPREAD] : 0;
-  if (sw.weights && wspr)
+  if (sw.weights && !sw.pol && wspr)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over a SelectorSpread queue would drop the handle's "
                                        "spread priority (weights = NULL sweeps under the whole configured policy)", who);
   // ... and the inter-pod weight of a pod that reads InterPodAffinityPriority
@@ -352,16 +379,19 @@ int sweep_general(Sweep& sw) {
   // a packed evaluation holds the map score (and a pod's spread and inter-pod scores) in
   // KSIM_SWEEP_GENERAL_SCORE_BITS bits: 10 x (LeastRequested + MostRequested + Balanced + spread weight
   // + inter-pod weight)
+  // (ksim_sweep_policy: every scenario's own five weights, checked by the entry)
   std::vector<int64_t> w3;
-  if (int rc = sweep_weights(sw, wspr + wipa, ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10 - 1,
-                             ipa ? "map, spread and inter-pod scores" : "map scores", KSIM_SWEEP_GENERAL_SCORE_BITS, &w3))
-    return rc;
+  if (!sw.pol)
+    if (int rc = sweep_weights(sw, wspr + wipa, ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10 - 1,
+                               ipa ? "map, spread and inter-pod scores" : "map scores", KSIM_SWEEP_GENERAL_SCORE_BITS, &w3))
+      return rc;
   // scratch: a chunk of C scenarios' copies of every column a commit writes, their contexts and
   // outputs, every scenario's weights, the sweep's error word and the whole sweep's prefix queues
   // (off, pod, out_pre: uploaded once, indexed by global scenario); a SelectorSpread queue adds a
   // scenario's copy of the counted pairs and its affinity descriptor; ksim_sweep_affinity its copy of
   // the carried terms and its column of raw priority sums, and the residents (uploaded once);
-  // ksim_sweep_volumes a scenario's copy of the mount words and slot counts and its volume descriptor.
+  // ksim_sweep_volumes a scenario's copy of the mount words and slot counts and its volume descriptor;
+  // ksim_sweep_policy every scenario's whole weight row (uploaded once) and a scenario's outcome record.
   // One chunk is one launch.
   const size_t S = sw.S(), N = (size_t)n, P = sw.P();
   const size_t NS = (size_t)c.n_scalar, NP = (size_t)c.port_slots;
@@ -398,7 +428,7 @@ int sweep_general(Sweep& sw) {
     cols.req_scalar = cv.take<int64_t>(C * N * NS);
     cols.ports = cv.take<uint64_t>(C * N * NP);
     a.ctx = cv.take<KsimCtx>(C);
-    if (sw.weights) dw = cv.take<int64_t>(S * 3);
+    if (sw.weights) dw = cv.take<int64_t>(S * (sw.pol ? KSIM_NW : 3));
     derr = cv.take<int32_t>(1);
     d = carve_out(cv, C, sw);
     if (rq) prefix(cv, C);
@@ -421,12 +451,12 @@ int sweep_general(Sweep& sw) {
   const size_t b_rq = (rq ? ksim_sweep_measure(prefix, 0) : 0) + (ipa ? ksim_sweep_measure(residents, 0) : 0);
   const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + sw.MW() + why_bytes(sw.wcap) +
                      (spr ? CL * 4 + sizeof(KsimAff) : 0) + (ipa ? KL * 8 + N * 8 : 0) +
-                     (sw.vol ? N * (8 * VS + 4) + sizeof(KsimVol) : 0);
+                     (sw.vol ? N * (8 * VS + 4) + sizeof(KsimVol) : 0) + (sw.outcome ? KSIM_SWEEP_OUTCOME_WORDS * 4 : 0);
   const int32_t chunk = sweep_scratch(sw, &h->sw_scratch, &h->sw_scratch_bytes, per, b_rq, layout);
   if (!chunk) return KSIM_E_NOMEM;
   a.n_pods = (int32_t)count;
   a.first = first;
-  a.w = dw;
+  a.w = sw.pol ? nullptr : dw;  // (the context kernel then keeps the handle's; the policy kernel writes the rows)
   a.out_node = d.node;
   a.out_counter = d.counter;
   a.why = SwWhy{sw.wcap, d.why_pod, d.why_hist};
@@ -454,7 +484,8 @@ int sweep_general(Sweep& sw) {
   }
   if (sw.vol) vold.base = h->vol_h;  // every launch copies the handle's current mounts: its own are only read
   HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
-  if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
+  if (dw && sw.pol) HIPCHK(h, hipMemcpyAsync(dw, sw.weights, S * KSIM_NW * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+  else if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
   float ms = 0.f;
   for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
@@ -462,8 +493,12 @@ int sweep_general(Sweep& sw) {
     a.scen0 = s0;  // the chunk's first scenario: its row of the weights
     if (int rc = chunk_absent(sw, d, s0, nsc)) return rc;
     hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, spr ? &sprd : nullptr, ipa ? &affd : nullptr, sw.vol ? &vold : nullptr,
-                                             nsc, d.absent, sw.aw, derr, h->ev0, h->ev1, ksim_stream(h));
+                                             sw.pol ? dw : nullptr, nsc, d.absent, sw.aw, derr, h->ev0, h->ev1, ksim_stream(h));
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
+    if (sw.outcome) {  // the scenarios' final state, before the next chunk reuses the copies
+      e = ksim_sweep_outcome_launch(a.ctx, nsc, d.outcome, h->ev1, ksim_stream(h));
+      if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep outcome launch: %s", hipGetErrorString(e));
+    }
     HIPCHK(h, hipEventSynchronize(h->ev1));
     float c_ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
@@ -825,6 +860,50 @@ int ksim_sweep_volumes(ksim_handle* h, const uint32_t* absent, int32_t n_scen, c
   sw.aw = (int32_t)((h->ctx.n + 31) / 32);
   sw.vol = true;
   sw.res = res;
+  return sweep_general(sw);
+}
+
+int ksim_sweep_policy(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
+                      const ksim_sweep_residents* res, const ksim_sweep_requeue* rq, int64_t first, int64_t count,
+                      int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled, int32_t* out_rehosted,
+                      const ksim_sweep_failures* fail, const ksim_sweep_outcome* outcome, ksim_stats* st) {
+  const char* who = "ksim_sweep_policy";
+  if (!weights) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
+  if (outcome && (!outcome->listed || !outcome->used || !outcome->free_cpu || !outcome->free_mem))
+    return ksim_fail(h, KSIM_E_INVAL, "%s: an outcome without a listed, used, free_cpu or free_mem array", who);
+  if (int rc = check_failures(h, who, fail)) return rc;
+  if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
+  if (int rc = check_residents(h, who, res)) return rc;
+  {  // the weight rules, on the host alone
+    int32_t s = 0;
+    int slot = -1;
+    switch (ksim_policy_weight_rules(h->ctx.w, h->ctx.no_prio, weights, n_scen, KSIM_SWEEP_GENERAL_SCORE_BITS, &s, &slot)) {
+      case KSIM_POLICY_OK: break;
+      case KSIM_POLICY_NO_PRIORITIES:
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the handle has an empty prioritizer list (EqualPriority): there is no "
+                                           "policy to vary", who);
+      case KSIM_POLICY_RANGE:
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: weight out of range (%s is negative)", who, s,
+                         ksim_policy_slot_name(slot));
+      case KSIM_POLICY_RESTRICTED:
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: %s has a weight but the handle's policy has none (its "
+                                           "tables were not built: a scenario rescales or drops such a priority)", who, s,
+                         ksim_policy_slot_name(slot));
+      case KSIM_POLICY_SCORE:
+        return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario %d: map, spread and inter-pod scores exceed %d bits", who, s,
+                         KSIM_SWEEP_GENERAL_SCORE_BITS);
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
+  if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
+  Sweep sw{h, who, weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
+           rq ? out_rehosted : nullptr};
+  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
+  sw.vol = h->have_vol;  // the VOL instantiations when volume tables are loaded, else the plain, SPR or IPA ones
+  sw.pol = true;
+  sw.res = res;
+  sw.outcome = outcome;
   return sweep_general(sw);
 }
 

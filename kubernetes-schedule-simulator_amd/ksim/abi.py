@@ -147,6 +147,13 @@ class SweepResidents(C.Structure):
     _fields_ = [("n", C.c_int64), ("node", _i32p), ("aff_ident", _i32p), ("aff_class", _i32p)]
 
 
+class SweepOutcome(C.Structure):
+    """ksim_sweep_outcome (include/ksim_polsweep.h): the caller's arrays for the scenarios' outcome records."""
+    _fields_ = [("listed", _i32p), ("used", _i32p), ("free_cpu", _i32p), ("free_mem", _i32p)]
+
+
+OUTCOME_BUCKETS = 11  # KSIM_OUTCOME_BUCKETS: LeastRequestedPriority's per-resource scores 0..10
+SWEEP_GENERAL_SCORE_BITS = 27  # KSIM_SWEEP_GENERAL_SCORE_BITS (csrc/ksim_sweep.h)
 SCHEDULE_ONLY, SCHEDULE_ASSUME = 0, 1
 
 
@@ -280,6 +287,11 @@ def lib():
     L.ksim_sweep_volumes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepResidents),
                                      C.POINTER(SweepRequeue), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(Stats)]
+    # include/ksim_polsweep.h (likewise)
+    L.ksim_sweep_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(SweepResidents),
+                                    C.POINTER(SweepRequeue), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.POINTER(SweepFailures), C.POINTER(SweepOutcome),
+                                    C.POINTER(Stats)]
     podargs = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     L.ksim_schedule_one.argtypes = [C.c_void_p] + podargs + [C.c_int32, C.POINTER(Result)]
     L.ksim_pod_add.argtypes = [C.c_void_p, C.c_int64] + podargs

@@ -681,14 +681,41 @@ class GenericScheduler:
         node-sharded scheduler, more than abi.SWEEP_GENERAL_MAX_NODES nodes."""
         return self._sweep_owned("sweep_volumes", "ksim_sweep_volumes", absent, requeue, first, count, explain, bound)
 
-    def _sweep_owned(self, who, entry, absent, requeue, first, count, explain, bound):
-        """sweep_affinity / sweep_volumes: the entries whose scenarios own affinity or volume state."""
+    def policy_weights(self, scenarios):
+        """The weight rows of sweep_policy for this scheduler (policy_rows)."""
+        return policy_rows(self.cluster, self.predicates, self.prioritizers, scenarios, self.custom_priorities, self.na_add)
+
+    def sweep_policy(self, scenarios, absent=None, requeue=None, first=0, count=None, explain=None, bound=(),
+                     outcome=False):
+        """Policy what-ifs under the whole provider (ksim_sweep_policy, include/ksim_polsweep.h): every
+        scenario — a prioritizer list, as in sweep, that may weigh TaintToleration, NodeAffinity,
+        SelectorSpread and InterPodAffinity as well as the map priorities — schedules its queue on its
+        own copy of the node state, spread counts, affinity counts and mounts, under this scheduler's
+        predicates.  A scenario may rescale or drop a priority this scheduler's policy has; it cannot
+        add a reduce, spread or inter-pod priority the policy lacks (KsimUnsupported: the tables were
+        not built), and the addend priorities stay the scheduler's (policy_weights).  absent: one node
+        set per scenario (outage x policy), or None; requeue: one prefix list per scenario as in
+        sweep_drain, or None; bound: as in sweep_affinity.  Returns what sweep returns, or what
+        sweep_drain returns when requeue is given; last_scheduled, last_rehosted and last_failures as
+        those calls set them.  outcome=True: self.last_outcome = dict(listed [n_scen], used [n_scen]
+        listed nodes holding a pod, free_cpu / free_mem [n_scen][abi.OUTCOME_BUCKETS] listed nodes by
+        LeastRequestedPriority's per-resource score of their final state), reduced on the device.
+        Always the general form."""
+        w = self.policy_weights(scenarios)
+        return self._sweep_owned("sweep_policy", "ksim_sweep_policy", absent, requeue, first, count, explain, bound,
+                                 weights=w, outcome=outcome)
+
+    def _sweep_owned(self, who, entry, absent, requeue, first, count, explain, bound, weights=None, outcome=False):
+        """sweep_affinity / sweep_volumes / sweep_policy: the entries whose scenarios own affinity or
+        volume state.  weights (sweep_policy): the scenarios' rows, which then give the scenario count."""
         n = len(self._pods)
         count = n - first if count is None else count
         mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
-        if requeue is None and mask is None:
+        if requeue is None and mask is None and weights is None:
             raise abi.KsimError(abi.E_INVAL, "%s: neither absent sets nor re-queue lists" % who)
-        S = len(requeue) if requeue is not None else len(mask)
+        S = len(weights) if weights is not None else len(requeue) if requeue is not None else len(mask)
+        if requeue is not None and len(requeue) != S:
+            raise abi.KsimError(abi.E_INVAL, "%s: %d scenarios but %d re-queue lists" % (who, S, len(requeue)))
         if mask is not None and len(mask) != S:
             raise abi.KsimError(abi.E_INVAL, "%s: %d re-queue lists but %d absent sets" % (who, S, len(mask)))
         res = [np.asarray(self.cluster.residents, np.int32).reshape(-1, 3)]
@@ -721,8 +748,21 @@ class GenericScheduler:
             f = C.byref(abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
                                           abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32)))
         st = abi.Stats()
-        self.h.call(entry, abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out), abi.vptr(ctr),
-                    abi.vptr(sched), abi.vptr(rehosted), f, C.byref(st))
+        if weights is None:
+            self.h.call(entry, abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out), abi.vptr(ctr),
+                        abi.vptr(sched), abi.vptr(rehosted), f, C.byref(st))
+        else:
+            oc = rec = None
+            if outcome:
+                rec = dict(listed=np.zeros(S, np.int32), used=np.zeros(S, np.int32),
+                           free_cpu=np.zeros((S, abi.OUTCOME_BUCKETS), np.int32),
+                           free_mem=np.zeros((S, abi.OUTCOME_BUCKETS), np.int32))
+                oc = C.byref(abi.SweepOutcome(*(abi.ptr(rec[k], C.c_int32) for k in ("listed", "used", "free_cpu", "free_mem"))))
+            weights = np.ascontiguousarray(weights, np.int64)
+            self.h.call(entry, abi.vptr(weights), abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out),
+                        abi.vptr(ctr), abi.vptr(sched), abi.vptr(rehosted), f, oc, C.byref(st))
+            if rec is not None:
+                self.last_outcome = rec
         self.last_stats = st
         self.last_scheduled = sched
         if fails is not None:
@@ -787,6 +827,36 @@ class GenericScheduler:
 
     def close(self):
         self.h.close()
+
+
+def policy_rows(cluster, predicates, priorities, scenarios, custom_priorities=None, na_add=None):
+    """The weight rows of GenericScheduler.sweep_policy, [len(scenarios)][abi.NW], for a scheduler over
+    `cluster` with these predicates and priorities (na_add: its per-class addends, Plan.na_add): each
+    scenario's prioritizer list through make_config with the cluster's spread flag.  The addends the
+    scheduler loaded (NodePreferAvoidPods, ImageLocality and the Policy's label priorities) stay its
+    own in every scenario, so a scenario must name every priority folded into them, at the scheduler's
+    weight, and none that would need addends the scheduler did not load; where they are constants on
+    every node they may differ freely, as every constant may.  Unsupported otherwise, and for an empty
+    scenario.  Needs no device."""
+    custom = dict(custom_priorities or {})
+    folding = {"NodePreferAvoidPodsPriority", "ImageLocalityPriority"} | set(custom)
+    own = sorted((n, int(x)) for n, x in priorities if n in folding)
+    spread = bool(getattr(cluster, "spread_active", False))
+    w = np.zeros((len(scenarios), abi.NW), np.int64)
+    for k, pri in enumerate(scenarios):
+        pri = list(pri)
+        if not pri:
+            raise Unsupported("sweep_policy: scenario %d is empty (EqualPriority is no policy to compare)" % k)
+        cfg = make_config(predicates, [(n, x) for n, x in pri if n not in custom], spread=spread, configured=pri)
+        folded = na_add is not None
+        if not folded:  # would this list, on this cluster, need addends?
+            folded = class_tables_for(cluster.tables, pri, cluster.label_sets.items, custom)[1] is not None
+        if folded and sorted((n, int(x)) for n, x in pri if n in folding) != own:
+            raise Unsupported("sweep_policy: scenario %d: %s differ across the nodes here and are folded into the "
+                              "scheduler's per-class addends; a scenario must name them at the scheduler's own weights %r"
+                              % (k, ", ".join(sorted(folding)), own))
+        w[k] = list(cfg.weights)
+    return w
 
 
 def absent_mask(n_nodes, sets):
@@ -1073,6 +1143,21 @@ class ClusterCapacity:
         rep.review = get_report(rep.status)
         return rep
 
+    def _outage_ranks(self, outages):
+        """The sorted node ranks of every (name, node names or indices) outage."""
+        cl = self.cluster
+        sets_ = []
+        for name, members in outages:
+            idx = []
+            for m in members:
+                if isinstance(m, str):
+                    if m not in cl.index:
+                        raise abi.KsimError(abi.E_INVAL, "outage %r: no node named %r" % (name, m))
+                    m = cl.index[m]
+                idx.append(int(m))
+            sets_.append(sorted(set(idx)))
+        return sets_
+
     def what_if(self, outages, first=0, count=None, explain=False):
         """Node-outage what-ifs over the snapshot (ksim_sweep_nodes): for every outage — (name, node
         names or indices), or the output of outage_sets — the whole queue is scheduled on the
@@ -1100,16 +1185,7 @@ class ClusterCapacity:
         failed pods fit_errors holds (all of them, or the cap)."""
         cl = self.cluster
         outages = list(outages)
-        sets_ = []
-        for name, members in outages:
-            idx = []
-            for m in members:
-                if isinstance(m, str):
-                    if m not in cl.index:
-                        raise abi.KsimError(abi.E_INVAL, "outage %r: no node named %r" % (name, m))
-                    m = cl.index[m]
-                idx.append(int(m))
-            sets_.append(sorted(set(idx)))
+        sets_ = self._outage_ranks(outages)
         if not outages:
             return []
         predicates, priorities, kw = self._sched_args
@@ -1142,6 +1218,59 @@ class ClusterCapacity:
                     for k in range(kept)])
         return recs
 
+    def policy_what_if(self, policies, outages=None, first=0, count=None, explain=False):
+        """Policy what-ifs over the snapshot (ksim_sweep_policy, GenericScheduler.sweep_policy): for
+        every policy — (name, prioritizer list) — the whole queue is scheduled on the snapshot under
+        the simulator's own predicates and that list, all policies in one sweep, on a scheduler of its
+        own that starts from the snapshot as loaded.  A policy may rescale or drop what the
+        simulator's provider or policy weighs (TaintToleration, NodeAffinity, SelectorSpread,
+        InterPodAffinity and the map priorities at will); what sweep_policy refuses is refused here.
+        outages: as in what_if — then one record per (policy, outage) pair, policy-major, still in one
+        sweep; an absent node vanishes with its running pods and nothing is re-queued.
+        Returns the records of what_if — dict(name (the outage's, None without outages), absent,
+        scheduled, failed, placements) and with explain listed, explained, fit_errors — plus policy
+        (its name) and the outcome of its final state over the listed nodes: listed, used (nodes
+        holding a pod), free_cpu / free_mem (11 counts of nodes by LeastRequestedPriority's
+        per-resource score 0..10: how many nodes stay empty or nearly so, and how evenly)."""
+        cl = self.cluster
+        policies = [(name, list(pri)) for name, pri in policies]
+        if not policies:
+            return []
+        outages = None if outages is None else list(outages)
+        if outages is not None and not outages:
+            return []
+        sets_ = None if outages is None else self._outage_ranks(outages)
+        cases = [(pn, pri, None, None) for pn, pri in policies] if outages is None else \
+            [(pn, pri, on, idx) for pn, pri in policies for (on, _), idx in zip(outages, sets_)]
+        predicates, priorities, kw = self._sched_args
+        g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
+        try:
+            out, _, _ = g.sweep_policy([c[1] for c in cases], None if outages is None else [c[3] for c in cases],
+                                       None, first, count, explain=explain if explain else None, outcome=True)
+            fails = g.last_failures if explain else None
+            oc = g.last_outcome
+        finally:
+            g.close()
+        names = cl.names
+        pod_names = cl.pod_names[first:first + out.shape[1]]
+        recs = []
+        for s, ((pn, _, on, idx), row) in enumerate(zip(cases, out)):
+            bound = int((row >= 0).sum())
+            recs.append(dict(policy=pn, name=on, absent=len(idx or ()), scheduled=bound, failed=len(row) - bound,
+                             placements=[(q, names[w] if w >= 0 else None) for q, w in zip(pod_names, row)],
+                             listed=int(oc["listed"][s]), used=int(oc["used"][s]),
+                             free_cpu=[int(v) for v in oc["free_cpu"][s]], free_mem=[int(v) for v in oc["free_mem"][s]]))
+            if fails is not None:
+                from .report import ERR_NO_NODES
+                listed = int(fails["listed"][s])
+                kept = min(int(fails["count"][s]), fails["pod"].shape[1])
+                scal = cl.scalar_names.items
+                recs[-1].update(explained=kept, fit_errors=[
+                    (pod_names[int(fails["pod"][s, k])],
+                     fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
+                    for k in range(kept)])
+        return recs
+
     def drain_what_if(self, outages, first=0, count=None, explain=False, evictable=None):
         """what_if with the pods of the lost nodes re-queued (ksim_sweep_drain): for every outage the
         evictable running pods bound to its nodes are scheduled first, as the copies a controller
@@ -1169,16 +1298,7 @@ class ClusterCapacity:
         if not outages:
             return []
         evictable = default_evictable if evictable is None else evictable
-        sets_ = []
-        for name, members in outages:
-            idx = []
-            for m in members:
-                if isinstance(m, str):
-                    if m not in cl.index:
-                        raise abi.KsimError(abi.E_INVAL, "outage %r: no node named %r" % (name, m))
-                    m = cl.index[m]
-                idx.append(int(m))
-            sets_.append(sorted(set(idx)))
+        sets_ = self._outage_ranks(outages)
         nq = len(self.order)
         count = nq - first if count is None else count
         lost = set().union(*sets_)
