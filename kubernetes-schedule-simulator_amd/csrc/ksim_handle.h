@@ -45,11 +45,7 @@ extern "C" hipError_t ksim_sweep_launch(const int64_t* rc0, const int64_t* rm0, 
                                         const int32_t* c0, const ksim_pod* pods, void* fpods, const SwArgsWhy* args,
                                         int32_t n_scen, const uint32_t* absent, int32_t absent_words, hipEvent_t ev0,
                                         hipEvent_t ev1, hipStream_t st);
-extern "C" hipError_t ksim_sweep_general_launch(const KsimCtx* hc, const SwgCols* cols, const SwgArgsPre* args,
-                                                const SwgSpread* spr, const SwgAffinity* ipa, const SwgVolumes* vol,
-                                                const int64_t* polw, int32_t n_scen, const uint32_t* absent,
-                                                int32_t absent_words, int32_t* err, hipEvent_t ev0, hipEvent_t ev1,
-                                                hipStream_t st);
+extern "C" hipError_t ksim_sweep_general_launch(const SwgLaunch* L);
 extern "C" int ksim_pfast_config(int64_t n, int max_grid, int stream, int* grid, int* lds_rows);
 extern "C" hipError_t ksim_pstream_prepare(const KsimCtx* c, double* mirror, hipStream_t s);
 extern "C" size_t ksim_pfast_granule_bytes(void);

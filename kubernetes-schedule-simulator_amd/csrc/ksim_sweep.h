@@ -132,6 +132,25 @@ struct SwgVolumes {
   KsimVol* vol;         // [C]
 };
 
+// One launch of the general form over a chunk, as ksim_sweep_general_launch takes it.  The feature parts
+// say which per-scenario state the sweep owns, and so which init kernels run and which instantiation
+// is launched: a null part = no such state.  ipa needs spr; vol goes with either, both or neither.
+struct SwgLaunch {
+  const KsimCtx* hc;       // the handle's context
+  const SwgCols* cols;     // the chunk's scenario columns
+  const SwgArgsPre* args;  // off set: the PRE instantiations; off / pod / out_pre indexed by scen0 + the chunk's scenario
+  const SwgSpread* spr;    // SelectorSpread state: the count copies and descriptors (the SPR instantiations)
+  const SwgAffinity* ipa;  // inter-pod affinity terms: carried copies, raw columns, residents (the IPA instantiations)
+  const SwgVolumes* vol;   // mounts: the mount copies and descriptors (the VOL instantiations)
+  const int64_t* polw;     // ksim_sweep_policy: the whole sweep's [S][KSIM_NW] weight rows (args->w is then null)
+  int32_t n_scen;          // scenarios of the chunk
+  const uint32_t* absent;  // [n_scen][absent_words] the chunk's node sets, or null
+  int32_t absent_words;
+  int32_t* err;            // the sweep's own error word (the handle's is never written)
+  hipEvent_t ev0, ev1;     // recorded before and behind the sweep kernel (may be null)
+  hipStream_t st;
+};
+
 // Policy sweeps (ksim_sweep_policy, include/ksim_polsweep.h, ksim_sweep_policy.hip): no instantiation
 // of their own.  The sweep kernels read all seven weights from the scenario's KsimCtx, so a policy
 // scenario is the handle's context with its whole weight row written over it

@@ -7,9 +7,11 @@
 // for resource-only ranges, the general form (ksim_sweep_general_kernel) for every other.  A form
 // states its per-scenario byte estimate, writes its scratch layout once (ksim_sweep_plan.h) and runs
 // its launches; the chunk rule, the scratch (re)allocation, the weight checks, the per-chunk copies
-// and the statistics are written once, below.
+// and the statistics are written once, below.  The general form decides once which per-scenario state
+// a sweep owns (SwgPlan, with ksim_sweep_admit.h for what table facts decide) and runs in steps over it.
 #include "ksim_handle.h"
 #include "ksim_polsweep_rules.h"
+#include "ksim_sweep_admit.h"
 #include "ksim_sweep_plan.h"
 
 #include "../../include/ksim_affsweep.h"
@@ -32,21 +34,21 @@ size_t why_bytes(int32_t cap) { return (size_t)cap * (1 + KSIM_NREASONS) * 4; }
 // listed in that scenario; weights NULL = the handle's own; rq (ksim_sweep_drain): every scenario's
 // prefix queue, scheduled before the range (count may then be 0).
 struct Sweep {
-  ksim_handle* h;
-  const char* who;
-  const int64_t* weights;
-  const uint32_t* absent;
-  int32_t n_scen;
-  int64_t first, count;
-  int32_t* out_node;
-  uint64_t* out_counters;
-  int32_t* out_scheduled;
-  const ksim_sweep_failures* fail;
-  ksim_stats* st;
-  const ksim_sweep_requeue* rq;
-  int32_t* out_rehosted;
-  int32_t aw;    // node-set words per scenario
-  int32_t wcap;  // records of failed pods a scenario keeps on the device (0: none)
+  ksim_handle* h = nullptr;
+  const char* who = "";
+  const int64_t* weights = nullptr;
+  const uint32_t* absent = nullptr;
+  int32_t n_scen = 0;
+  int64_t first = 0, count = 0;
+  int32_t* out_node = nullptr;
+  uint64_t* out_counters = nullptr;
+  int32_t* out_scheduled = nullptr;
+  const ksim_sweep_failures* fail = nullptr;
+  ksim_stats* st = nullptr;
+  const ksim_sweep_requeue* rq = nullptr;
+  int32_t* out_rehosted = nullptr;
+  int32_t aw = 0;    // node-set words per scenario
+  int32_t wcap = 0;  // records of failed pods a scenario keeps on the device (0: none)
   // ksim_sweep_affinity: the tables' inter-pod affinity terms are swept (the IPA instantiations), every
   // scenario's counts less the residents on its absent nodes (res may be null: nothing is corrected)
   bool ipa = false;
@@ -55,8 +57,8 @@ struct Sweep {
   // on its own copy of the mounts; affinity terms in the tables are swept as by ksim_sweep_affinity
   bool vol = false;
   // ksim_sweep_policy: weights holds whole rows, [n_scen][KSIM_NW], checked by the entry
-  // (ksim_policy_weight_rules); the queue takes whichever instantiation it would without weights, and
-  // outcome (may be null) receives every scenario's record
+  // (ksim_policy_weight_rules); the queue takes whichever instantiation it would without weights (the
+  // VOL ones when volume tables are loaded), and outcome (may be null) receives every scenario's record
   bool pol = false;
   const ksim_sweep_outcome* outcome = nullptr;
 
@@ -288,58 +290,61 @@ void sweep_done(const Sweep& sw, int32_t chunk, int32_t mode, float device_ms, f
   }
 }
 
-// The general form of the sweep (ksim_sweep_general_kernel): a range with a pod that is not
-// resource-only, or prefix queues (sw.rq, which ksim_sweep_drain has checked; weights are then NULL).
-int sweep_general(Sweep& sw) {
+// ---- The general form of the sweep (ksim_sweep_general_kernel): a range with a pod that is not
+// resource-only, or prefix queues (sw.rq, which the entry has checked).  Five steps over one plan:
+// admit (the plan or the refusal), layout, upload, run, verdict.
+
+// Which per-scenario state this sweep owns and what its packed score carries.  swg_admit decides it
+// once; the layout, the uploads, the launch description and the verdict read nothing else.
+struct SwgPlan {
+  bool spr = false;  // a scenario's copy of the counted pairs and its affinity descriptor (the SPR instantiations)
+  bool ipa = false;  // ... its carried terms and raw priority sums, and the residents (the IPA instantiations)
+  bool vol = false;  // ... its mount words, slot counts and volume descriptor (the VOL instantiations)
+  bool pol = false;  // every scenario's whole weight row, checked by the entry (ksim_sweep_policy)
+  // the spread / inter-pod weight a pod's packed score carries beside the map weights
+  int64_t wspr = 0, wipa = 0;
+  size_t CL = 0, KL = 0, R = 0, VS = 0;  // words of a scenario's counted pairs / carried terms, residents, volume slots
+  std::vector<int64_t> w3;               // [S][3] map weights (not pol)
+};
+
+// The messages of ksim_sweep_admit.h's codes.  A table-level refusal takes (who, zones, zone cap); a spread
+// bar is the " (why)" behind the refusal of a queue pod with affinity or spread state and takes (zones, zone cap).
+const char* const SWG_REFUSAL[] = {nullptr,
+    "%s: no volume tables are loaded (ksim_sweep_nodes, ksim_sweep_drain and ksim_sweep_affinity sweep such a queue)",
+    "%s: no affinity tables are loaded (ksim_sweep_nodes and ksim_sweep_drain sweep such a queue)",
+    "%s: %d zones exceed the %d zones of a swept SelectorSpread queue (an affinity class has a spread pair)"};
+const char* const SWG_SPREAD_BAR[] = {
+    "", " (the tables hold inter-pod affinity terms: only SelectorSpread state is swept)",
+    " (auxiliary spreading priority or lender tables are loaded)",
+    " (%d zones exceed the %d zones of a swept SelectorSpread queue)"};
+
+// Admit: the plan of this sweep, or its refusal.  Table-level refusals first (ksim_sweep_admit.h decides
+// them and which state is owned, from table facts alone), then the range, then the sorted distinct prefix
+// pods, then the weights.  A pod with affinity state is swept when that state is SelectorSpread's alone or
+// the sweep owns the inter-pod terms (k.spread_bar open); a pod that mounts volumes when it owns the mounts.
+int swg_admit(const Sweep& sw, SwgPlan* p) {
   ksim_handle* h = sw.h;
   const char* who = sw.who;
-  const ksim_sweep_requeue* rq = sw.rq;
+  const KsimCtx& c = h->ctx;
   const int64_t first = sw.first, count = sw.count;
-  const int32_t n_scen = sw.n_scen;
-  KsimCtx& c = h->ctx;
-  const int64_t n = c.n;
-  const size_t T = sw.T();
-  int64_t mmax = 0;
-  for (int32_t s = 0; rq && s < n_scen; ++s) mmax = std::max(mmax, rq->off[s + 1] - rq->off[s]);
-  sw.set_wcap(mmax + count);  // over the longest scenario queue
   if (h->shard.world > 1) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a node-sharded handle sweeps resource-only pods only", who);
-  if (n > KSIM_SWEEP_GENERAL_MAX_NODES)
+  if (c.n > KSIM_SWEEP_GENERAL_MAX_NODES)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %lld nodes exceed the %d-node scenario layout of pods that are not "
-                                       "resource-only", who, (long long)n, KSIM_SWEEP_GENERAL_MAX_NODES);
-  // A pod with affinity state is swept when that state is SelectorSpread's alone (the SPR
-  // instantiations): no affinity / anti-affinity term of any pod class, no term carried by a running
-  // pod, no auxiliary or lender tables, and the zones within the kernel's LDS words.
-  // ksim_sweep_affinity (sw.ipa) sweeps those terms too (the IPA instantiations), over every range:
-  // it needs the tables, refuses the zones only where a class has a spread pair (else the zone words
-  // stay unused), and auxiliary or lender tables by the refusal every range gets below.
-  // ksim_sweep_volumes (sw.vol) takes the IPA instantiations when the tables hold such terms, and else
-  // the SPR or plain ones by the rule of every range; it needs the volume tables.
-  const bool terms = h->have_aff && (h->aff_n_carry || h->pg_max_req || h->pg_max_pref || h->pg_max_car);
-  // ksim_sweep_policy (sw.pol) chooses as ksim_sweep_volumes does, with sw.vol = volume tables are loaded.
-  const bool ipa = sw.ipa || ((sw.vol || sw.pol) && terms);
-  if (sw.vol && !h->have_vol)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: no volume tables are loaded (ksim_sweep_nodes, ksim_sweep_drain and "
-                                       "ksim_sweep_affinity sweep such a queue)", who);
-  if (ipa && !h->have_aff)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: no affinity tables are loaded (ksim_sweep_nodes and ksim_sweep_drain sweep "
-                                       "such a queue)", who);
-  if (ipa && h->aff_n_zone > KSIM_SWEEP_SPREAD_MAX_ZONES && h->aff_any_spread)
-    return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: %d zones exceed the %d zones of a swept SelectorSpread queue (an affinity "
-                                       "class has a spread pair)", who, h->aff_n_zone, KSIM_SWEEP_SPREAD_MAX_ZONES);
-  char spr_no[96] = "";
-  if (h->have_aff && !ipa) {
-    if (terms)
-      snprintf(spr_no, sizeof spr_no, " (the tables hold inter-pod affinity terms: only SelectorSpread state is swept)");
-    else if (ksim_rt_launch_tables(h))
-      snprintf(spr_no, sizeof spr_no, " (auxiliary spreading priority or lender tables are loaded)");
-    else if (h->aff_n_zone > KSIM_SWEEP_SPREAD_MAX_ZONES)
-      snprintf(spr_no, sizeof spr_no, " (%d zones exceed the %d zones of a swept SelectorSpread queue)", h->aff_n_zone,
-               KSIM_SWEEP_SPREAD_MAX_ZONES);
-  }
-  bool spr = ipa || ksim_rt_aff_count(h, first, count) > 0;
-  if (spr && spr_no[0])
+                                       "resource-only", who, (long long)c.n, KSIM_SWEEP_GENERAL_MAX_NODES);
+  KsimSweepFacts f{};
+  f.have_aff = h->have_aff; f.have_vol = h->have_vol; f.launch_tables = ksim_rt_launch_tables(h);
+  f.n_carry = h->aff_n_carry; f.max_req = h->pg_max_req; f.max_pref = h->pg_max_pref; f.max_car = h->pg_max_car;
+  f.n_zone = h->aff_n_zone; f.max_zones = KSIM_SWEEP_SPREAD_MAX_ZONES; f.any_spread = h->aff_any_spread;
+  f.ipa = sw.ipa; f.vol = sw.vol; f.pol = sw.pol;
+  const KsimSweepKind k = ksim_sweep_admit_tables(f);
+  if (k.refusal)
+    return ksim_fail(h, KSIM_E_UNSUPPORTED, SWG_REFUSAL[k.refusal], who, h->aff_n_zone, KSIM_SWEEP_SPREAD_MAX_ZONES);
+  char spr_no[96];
+  snprintf(spr_no, sizeof spr_no, SWG_SPREAD_BAR[k.spread_bar], h->aff_n_zone, KSIM_SWEEP_SPREAD_MAX_ZONES);
+  p->spr = k.ipa || ksim_rt_aff_count(h, first, count) > 0;
+  if (p->spr && spr_no[0])
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod in the range carries inter-pod affinity or spread state%s", who, spr_no);
-  for (int64_t q = first; !sw.vol && q < first + count; ++q)
+  for (int64_t q = first; !k.vol && q < first + count; ++q)
     if (h->q_vclass[q]) return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: pod %lld mounts volumes", who, (long long)q);
   if (ksim_rt_launch_tables(h))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: an auxiliary spreading priority or CheckServiceAffinity's lender table is "
@@ -347,8 +352,8 @@ int sweep_general(Sweep& sw) {
   if (ksim_rt_range_wide(h, first, count))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: a pod class in the range has more than %d reduce classes", who,
                 KSIM_MAX_RCLASS);
-  if (T) {  // the same refusals for the distinct prefix pods
-    std::vector<int64_t> idx(rq->pod, rq->pod + T);
+  if (sw.T()) {  // the same refusals for the sorted distinct prefix pods
+    std::vector<int64_t> idx(sw.rq->pod, sw.rq->pod + sw.T());
     std::sort(idx.begin(), idx.end());
     idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
     for (int64_t q : idx) {
@@ -356,170 +361,200 @@ int sweep_general(Sweep& sw) {
         if (spr_no[0])
           return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld carries inter-pod affinity or spread state%s", who,
                       (long long)q, spr_no);
-        spr = true;
+        p->spr = true;
       }
-      if (!sw.vol && h->q_vclass[q])
+      if (!k.vol && h->q_vclass[q])
         return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: re-queued pod %lld mounts volumes", who, (long long)q);
       if (ksim_rt_range_wide(h, q, 1))
         return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: the class of re-queued pod %lld has more than %d reduce classes", who,
                     (long long)q, KSIM_MAX_RCLASS);
     }
   }
+  p->ipa = k.ipa; p->vol = k.vol; p->pol = sw.pol;
   if (sw.weights && !sw.pol && (c.w[KSIM_W_TAINT_TOLERATION] || c.w[KSIM_W_NODE_AFFINITY] || c.use_na))
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over pods that are not resource-only would drop the "
                                        "handle's reduce priorities or NodePreferAvoidPods addend (weights = NULL sweeps "
                                        "under the whole configured policy)", who);
-  // the spread weight a spread pod's packed score carries beside the map weights
-  const int64_t wspr = (spr && !c.no_prio) ? c.w[KSIM_W_SELECTOR_SPREAD] : 0;
-  if (sw.weights && !sw.pol && wspr)
+  p->wspr = (p->spr && !c.no_prio) ? c.w[KSIM_W_SELECTOR_SPREAD] : 0;
+  if (sw.weights && !sw.pol && p->wspr)
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "%s: scenario weights over a SelectorSpread queue would drop the handle's "
                                        "spread priority (weights = NULL sweeps under the whole configured policy)", who);
-  // ... and the inter-pod weight of a pod that reads InterPodAffinityPriority
-  const int64_t wipa = (ipa && !c.no_prio) ? c.w[KSIM_W_INTERPOD_AFFINITY] : 0;
+  p->wipa = (p->ipa && !c.no_prio) ? c.w[KSIM_W_INTERPOD_AFFINITY] : 0;
+  p->CL = p->spr ? (size_t)h->aff_cnt_len : 0; p->KL = p->ipa ? (size_t)h->aff_carried_len : 0;
+  p->R = p->ipa && sw.res ? (size_t)sw.res->n : 0; p->VS = p->vol ? (size_t)h->vol_h.vol_slots : 0;
   // a packed evaluation holds the map score (and a pod's spread and inter-pod scores) in
   // KSIM_SWEEP_GENERAL_SCORE_BITS bits: 10 x (LeastRequested + MostRequested + Balanced + spread weight
   // + inter-pod weight)
   // (ksim_sweep_policy: every scenario's own five weights, checked by the entry)
-  std::vector<int64_t> w3;
-  if (!sw.pol)
-    if (int rc = sweep_weights(sw, wspr + wipa, ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10 - 1,
-                               ipa ? "map, spread and inter-pod scores" : "map scores", KSIM_SWEEP_GENERAL_SCORE_BITS, &w3))
-      return rc;
-  // scratch: a chunk of C scenarios' copies of every column a commit writes, their contexts and
-  // outputs, every scenario's weights, the sweep's error word and the whole sweep's prefix queues
-  // (off, pod, out_pre: uploaded once, indexed by global scenario); a SelectorSpread queue adds a
-  // scenario's copy of the counted pairs and its affinity descriptor; ksim_sweep_affinity its copy of
-  // the carried terms and its column of raw priority sums, and the residents (uploaded once);
-  // ksim_sweep_volumes a scenario's copy of the mount words and slot counts and its volume descriptor;
-  // ksim_sweep_policy every scenario's whole weight row (uploaded once) and a scenario's outcome record.
-  // One chunk is one launch.
-  const size_t S = sw.S(), N = (size_t)n, P = sw.P();
-  const size_t NS = (size_t)c.n_scalar, NP = (size_t)c.port_slots;
-  const size_t CL = spr ? (size_t)h->aff_cnt_len : 0;
-  const size_t KL = ipa ? (size_t)h->aff_carried_len : 0, R = ipa && sw.res ? (size_t)sw.res->n : 0;
+  if (p->pol) return KSIM_OK;
+  return sweep_weights(sw, p->wspr + p->wipa, ((int64_t)1 << KSIM_SWEEP_GENERAL_SCORE_BITS) / 10 - 1,
+                       p->ipa ? "map, spread and inter-pod scores" : "map scores", KSIM_SWEEP_GENERAL_SCORE_BITS, &p->w3);
+}
+
+// The device arrays of a general sweep, as swg_layout hands them out, and the launch arguments over them.
+struct SwgScratch {
   SwgCols cols{};
   SwgArgsPre a{};
-  SwgSpread sprd{};
-  SwgAffinity affd{};
-  SwgVolumes vold{};
-  const size_t VS = sw.vol ? (size_t)h->vol_h.vol_slots : 0;
+  SwgSpread sprd{}; SwgAffinity affd{}; SwgVolumes vold{};  // the feature parts of a launch (SwgLaunch)
   SweepOut d{};
   // ksim_commit's port-slot overflow bit, and the mount commit's (the handle's word is not written)
-  int32_t* derr = nullptr;
-  int64_t *dw = nullptr, *doff = nullptr, *dpod = nullptr;
-  int32_t *rnode = nullptr, *rident = nullptr, *rclass = nullptr;
-  auto residents = [&](KsimSweepCarver& cv, size_t) {
-    rnode = cv.take<int32_t>(R);
-    rident = cv.take<int32_t>(R);
-    rclass = cv.take<int32_t>(R);
-    affd.bad = cv.take<int32_t>(1);
-  };
-  auto prefix = [&](KsimSweepCarver& cv, size_t) {
-    doff = cv.take<int64_t>(S + 1);
-    dpod = cv.take<int64_t>(T);
-    d.pre = cv.take<int32_t>(T);
-  };
-  auto layout = [&](KsimSweepCarver& cv, size_t C) {
-    cols.req_cpu = cv.take<int64_t>(C * N); cols.req_mem = cv.take<int64_t>(C * N);
-    cols.req_gpu = cv.take<int64_t>(C * N); cols.req_eph = cv.take<int64_t>(C * N);
-    cols.nz_cpu = cv.take<int64_t>(C * N); cols.nz_mem = cv.take<int64_t>(C * N);
-    cols.pod_count = cv.take<int32_t>(C * N); cols.port_count = cv.take<int32_t>(C * N);
-    cols.flags = cv.take<uint32_t>(C * N);
-    cols.req_scalar = cv.take<int64_t>(C * N * NS);
-    cols.ports = cv.take<uint64_t>(C * N * NP);
-    a.ctx = cv.take<KsimCtx>(C);
-    if (sw.weights) dw = cv.take<int64_t>(S * (sw.pol ? KSIM_NW : 3));
-    derr = cv.take<int32_t>(1);
-    d = carve_out(cv, C, sw);
-    if (rq) prefix(cv, C);
-    if (spr) {
-      sprd.cnt = cv.take<int32_t>(C * CL);
-      sprd.aff = cv.take<KsimAff>(C);
-    }
-    if (ipa) {
-      affd.carried = cv.take<int64_t>(C * KL);
-      affd.raw = cv.take<int64_t>(C * N);
-      residents(cv, C);
-    }
-    if (sw.vol) {
-      vold.slots = cv.take<uint64_t>(C * VS * N);
-      vold.slot_count = cv.take<int32_t>(C * N);
-      vold.vol = cv.take<KsimVol>(C);
-    }
-  };
-  // chunk-independent: off the budget first
-  const size_t b_rq = (rq ? ksim_sweep_measure(prefix, 0) : 0) + (ipa ? ksim_sweep_measure(residents, 0) : 0);
-  const size_t per = N * (60 + 8 * NS + 8 * NP) + sizeof(KsimCtx) + P * 4 + 8 + sw.MW() + why_bytes(sw.wcap) +
-                     (spr ? CL * 4 + sizeof(KsimAff) : 0) + (ipa ? KL * 8 + N * 8 : 0) +
-                     (sw.vol ? N * (8 * VS + 4) + sizeof(KsimVol) : 0) + (sw.outcome ? KSIM_SWEEP_OUTCOME_WORDS * 4 : 0);
-  const int32_t chunk = sweep_scratch(sw, &h->sw_scratch, &h->sw_scratch_bytes, per, b_rq, layout);
-  if (!chunk) return KSIM_E_NOMEM;
-  a.n_pods = (int32_t)count;
-  a.first = first;
-  a.w = sw.pol ? nullptr : dw;  // (the context kernel then keeps the handle's; the policy kernel writes the rows)
-  a.out_node = d.node;
-  a.out_counter = d.counter;
-  a.why = SwWhy{sw.wcap, d.why_pod, d.why_hist};
-  a.off = doff;
-  a.pod = dpod;
-  a.out_pre = d.pre;
-  if (rq) {
-    HIPCHK(h, hipMemcpyAsync(doff, rq->off, (S + 1) * 8, hipMemcpyHostToDevice, ksim_stream(h)));
-    if (T) HIPCHK(h, hipMemcpyAsync(dpod, rq->pod, T * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+  int32_t *err = nullptr, *rnode = nullptr, *rident = nullptr, *rclass = nullptr;
+  int64_t *w = nullptr, *off = nullptr, *pod = nullptr;
+};
+
+// Layout: a chunk of C scenarios' copies of every column a commit writes, their contexts and outputs,
+// every scenario's weights (whole rows for ksim_sweep_policy) and the sweep's error word; then, by the
+// plan, the state a scenario owns.  A new per-scenario state is one field of SwgPlan, its take()s here,
+// and its init kernel in ksim_sweep_general_launch.  One chunk is one launch.  The arrays without a C are
+// the whole sweep's, uploaded once: the weights, the prefix queues (off, pod, out_pre, indexed by global
+// scenario), the residents and the word for the scenario whose corrected counts are negative.
+void swg_layout(KsimSweepCarver& cv, size_t C, const Sweep& sw, const SwgPlan& p, SwgScratch& m) {
+  const size_t N = (size_t)sw.h->ctx.n, NS = (size_t)sw.h->ctx.n_scalar, NP = (size_t)sw.h->ctx.port_slots;
+  SwgCols& cols = m.cols;
+  cols.req_cpu = cv.take<int64_t>(C * N); cols.req_mem = cv.take<int64_t>(C * N);
+  cols.req_gpu = cv.take<int64_t>(C * N); cols.req_eph = cv.take<int64_t>(C * N);
+  cols.nz_cpu = cv.take<int64_t>(C * N); cols.nz_mem = cv.take<int64_t>(C * N);
+  cols.pod_count = cv.take<int32_t>(C * N); cols.port_count = cv.take<int32_t>(C * N);
+  cols.flags = cv.take<uint32_t>(C * N);
+  cols.req_scalar = cv.take<int64_t>(C * N * NS);
+  cols.ports = cv.take<uint64_t>(C * N * NP);
+  m.a.ctx = cv.take<KsimCtx>(C);
+  if (sw.weights) m.w = cv.take<int64_t>(sw.S() * (p.pol ? KSIM_NW : 3));
+  m.err = cv.take<int32_t>(1);
+  m.d = carve_out(cv, C, sw);
+  if (sw.rq) {
+    m.off = cv.take<int64_t>(sw.S() + 1);
+    m.pod = cv.take<int64_t>(sw.T());
+    m.d.pre = cv.take<int32_t>(sw.T());
   }
-  if (spr) {  // every launch copies the handle's current counts: the handle's own are only read
-    sprd.base = h->aff_h;
-    sprd.cnt_len = (int64_t)CL;
+  if (p.spr) {
+    m.sprd.cnt = cv.take<int32_t>(C * p.CL);
+    m.sprd.aff = cv.take<KsimAff>(C);
   }
-  if (ipa) {
-    affd.carried_len = (int64_t)KL;
-    affd.res = SwgResidents{(int64_t)R, rnode, rident, rclass};
+  if (p.ipa) {
+    m.affd.carried = cv.take<int64_t>(C * p.KL);
+    m.affd.raw = cv.take<int64_t>(C * N);
+    m.rnode = cv.take<int32_t>(p.R); m.rident = cv.take<int32_t>(p.R); m.rclass = cv.take<int32_t>(p.R);
+    m.affd.bad = cv.take<int32_t>(1);
+  }
+  if (p.vol) {
+    m.vold.slots = cv.take<uint64_t>(C * p.VS * N);
+    m.vold.slot_count = cv.take<int32_t>(C * N);
+    m.vold.vol = cv.take<KsimVol>(C);
+  }
+}
+
+// Upload: the launch arguments over the scratch, and the once-per-sweep copies: prefix lists, residents,
+// weight rows, error word.
+int swg_upload(const Sweep& sw, const SwgPlan& p, SwgScratch& m) {
+  ksim_handle* h = sw.h;
+  const size_t S = sw.S(), T = sw.T(), R = p.R;
+  SwgArgsPre& a = m.a;
+  a.n_pods = (int32_t)sw.count; a.first = sw.first;
+  a.w = p.pol ? nullptr : m.w;  // (the context kernel then keeps the handle's; the policy kernel writes the rows)
+  a.out_node = m.d.node; a.out_counter = m.d.counter;
+  a.why = SwWhy{sw.wcap, m.d.why_pod, m.d.why_hist};
+  a.off = m.off; a.pod = m.pod; a.out_pre = m.d.pre;
+  if (sw.rq) {
+    HIPCHK(h, hipMemcpyAsync(m.off, sw.rq->off, (S + 1) * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+    if (T) HIPCHK(h, hipMemcpyAsync(m.pod, sw.rq->pod, T * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+  }
+  if (p.spr) {  // every launch copies the handle's current counts: the handle's own are only read
+    m.sprd.base = h->aff_h;
+    m.sprd.cnt_len = (int64_t)p.CL;
+  }
+  if (p.ipa) {
+    m.affd.carried_len = (int64_t)p.KL;
+    m.affd.res = SwgResidents{(int64_t)R, m.rnode, m.rident, m.rclass};
     const int32_t none = INT32_MAX;
-    HIPCHK(h, hipMemcpyAsync(affd.bad, &none, 4, hipMemcpyHostToDevice, ksim_stream(h)));
+    HIPCHK(h, hipMemcpyAsync(m.affd.bad, &none, 4, hipMemcpyHostToDevice, ksim_stream(h)));
     if (R) {
-      HIPCHK(h, hipMemcpyAsync(rnode, sw.res->node, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
-      HIPCHK(h, hipMemcpyAsync(rident, sw.res->aff_ident, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
-      HIPCHK(h, hipMemcpyAsync(rclass, sw.res->aff_class, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
+      HIPCHK(h, hipMemcpyAsync(m.rnode, sw.res->node, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
+      HIPCHK(h, hipMemcpyAsync(m.rident, sw.res->aff_ident, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
+      HIPCHK(h, hipMemcpyAsync(m.rclass, sw.res->aff_class, R * 4, hipMemcpyHostToDevice, ksim_stream(h)));
     }
   }
-  if (sw.vol) vold.base = h->vol_h;  // every launch copies the handle's current mounts: its own are only read
-  HIPCHK(h, hipMemcpy(&a.counter0, c.counter, 8, hipMemcpyDeviceToHost));
-  if (dw && sw.pol) HIPCHK(h, hipMemcpyAsync(dw, sw.weights, S * KSIM_NW * 8, hipMemcpyHostToDevice, ksim_stream(h)));
-  else if (dw) HIPCHK(h, hipMemcpyAsync(dw, w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
-  HIPCHK(h, hipMemsetAsync(derr, 0, 4, ksim_stream(h)));
-  float ms = 0.f;
-  for (int32_t s0 = 0; s0 < n_scen; s0 += chunk) {
-    const int32_t nsc = std::min(chunk, n_scen - s0);
-    a.scen0 = s0;  // the chunk's first scenario: its row of the weights
-    if (int rc = chunk_absent(sw, d, s0, nsc)) return rc;
-    hipError_t e = ksim_sweep_general_launch(&c, &cols, &a, spr ? &sprd : nullptr, ipa ? &affd : nullptr, sw.vol ? &vold : nullptr,
-                                             sw.pol ? dw : nullptr, nsc, d.absent, sw.aw, derr, h->ev0, h->ev1, ksim_stream(h));
+  if (p.vol) m.vold.base = h->vol_h;  // every launch copies the handle's current mounts: its own are only read
+  HIPCHK(h, hipMemcpy(&a.counter0, h->ctx.counter, 8, hipMemcpyDeviceToHost));
+  if (m.w && p.pol) HIPCHK(h, hipMemcpyAsync(m.w, sw.weights, S * KSIM_NW * 8, hipMemcpyHostToDevice, ksim_stream(h)));
+  else if (m.w) HIPCHK(h, hipMemcpyAsync(m.w, p.w3.data(), S * 24, hipMemcpyHostToDevice, ksim_stream(h)));
+  HIPCHK(h, hipMemsetAsync(m.err, 0, 4, ksim_stream(h)));
+  return KSIM_OK;
+}
+
+// Run: the chunk loop.  The plan's flags become the launch description's feature parts here and nowhere else.
+int swg_run(const Sweep& sw, const SwgPlan& p, SwgScratch& m, int32_t chunk, float* ms) {
+  ksim_handle* h = sw.h;
+  SwgLaunch L{};
+  L.hc = &h->ctx; L.cols = &m.cols; L.args = &m.a;
+  L.spr = p.spr ? &m.sprd : nullptr;
+  L.ipa = p.ipa ? &m.affd : nullptr;
+  L.vol = p.vol ? &m.vold : nullptr;
+  L.polw = p.pol ? m.w : nullptr;
+  L.absent = m.d.absent; L.absent_words = sw.aw;
+  L.err = m.err; L.ev0 = h->ev0; L.ev1 = h->ev1;
+  for (int32_t s0 = 0; s0 < sw.n_scen; s0 += chunk) {
+    const int32_t nsc = std::min(chunk, sw.n_scen - s0);
+    m.a.scen0 = s0;  // the chunk's first scenario: its row of the weights
+    L.n_scen = nsc;
+    if (int rc = chunk_absent(sw, m.d, s0, nsc)) return rc;
+    L.st = ksim_stream(h);
+    hipError_t e = ksim_sweep_general_launch(&L);
     if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep launch: %s", hipGetErrorString(e));
     if (sw.outcome) {  // the scenarios' final state, before the next chunk reuses the copies
-      e = ksim_sweep_outcome_launch(a.ctx, nsc, d.outcome, h->ev1, ksim_stream(h));
+      e = ksim_sweep_outcome_launch(m.a.ctx, nsc, m.d.outcome, h->ev1, ksim_stream(h));
       if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "sweep outcome launch: %s", hipGetErrorString(e));
     }
     HIPCHK(h, hipEventSynchronize(h->ev1));
     float c_ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&c_ms, h->ev0, h->ev1));
-    ms += c_ms;
-    if (int rc = chunk_out(sw, d, s0, nsc)) return rc;
+    *ms += c_ms;
+    if (int rc = chunk_out(sw, m.d, s0, nsc)) return rc;
   }
+  return KSIM_OK;
+}
+
+// Verdict: the sweep's error word, after the last chunk.
+int swg_verdict(const Sweep& sw, const SwgPlan& p, const SwgScratch& m) {
+  ksim_handle* h = sw.h;
   int32_t err = 0;
-  HIPCHK(h, hipMemcpy(&err, derr, 4, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(&err, m.err, 4, hipMemcpyDeviceToHost));
   if (err & KSIM_SWEEP_ERR_COUNTS) {
     int32_t bad = 0;
-    HIPCHK(h, hipMemcpy(&bad, affd.bad, 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&bad, m.affd.bad, 4, hipMemcpyDeviceToHost));
     return ksim_fail(h, KSIM_E_INVAL, "%s: scenario %d: a counted pair is negative once the residents of its absent nodes "
-                                 "are taken out (the residents are not the placed pods behind the handle's counts)", who, bad);
+                                 "are taken out (the residents are not the placed pods behind the handle's counts)",
+                     sw.who, bad);
   }
-  if (err && sw.vol)
+  if (err && p.vol)
     return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's volume slots or host-port slots overflowed, or a mount count of a "
                                     "volume saturated, in a scenario (load the volume tables with more vol_slots, or the "
-                                    "node table with more port slots)", who);
+                                    "node table with more port slots)", sw.who);
   if (err)
     return ksim_fail(h, KSIM_E_OVERFLOW, "%s: a node's host-port slots overflowed in a scenario (load the node table with "
-                                    "more port slots)", who);
+                                    "more port slots)", sw.who);
+  return KSIM_OK;
+}
+
+int sweep_general(Sweep& sw) {
+  int64_t mmax = 0;
+  for (int32_t s = 0; sw.rq && s < sw.n_scen; ++s) mmax = std::max(mmax, sw.rq->off[s + 1] - sw.rq->off[s]);
+  sw.set_wcap(mmax + sw.count);  // over the longest scenario queue
+  SwgPlan p;
+  if (int rc = swg_admit(sw, &p)) return rc;
+  SwgScratch m;
+  auto layout = [&](KsimSweepCarver& cv, size_t C) { swg_layout(cv, C, sw, p, m); };
+  // From the layout itself: no scenario's arrays are the chunk-independent bytes, off the budget first; 256
+  // scenarios' arrays end on the carver's alignment, so the difference to none holds no padding and is a
+  // scenario's bytes.
+  constexpr size_t A = KsimSweepCarver::ALIGN;
+  const size_t fixed = ksim_sweep_measure(layout, 0), per = (ksim_sweep_measure(layout, A) - fixed) / A;
+  const int32_t chunk = sweep_scratch(sw, &sw.h->sw_scratch, &sw.h->sw_scratch_bytes, per, fixed, layout);
+  if (!chunk) return KSIM_E_NOMEM;
+  float ms = 0.f;
+  if (int rc = swg_upload(sw, p, m)) return rc;
+  if (int rc = swg_run(sw, p, m, chunk, &ms)) return rc;
+  if (int rc = swg_verdict(sw, p, m)) return rc;
   sweep_done(sw, chunk, KSIM_MODE_PERSISTENT, ms, ms);
   return KSIM_OK;
 }
@@ -787,6 +822,40 @@ int check_residents(ksim_handle* h, const char* who, const ksim_sweep_residents*
   return KSIM_OK;
 }
 
+// The arguments every entry has into a Sweep; an entry names its others itself.
+Sweep sweep_of(ksim_handle* h, const char* who, int32_t n_scen, int64_t first, int64_t count, int32_t* out_node,
+               uint64_t* out_counters, ksim_stats* st) {
+  Sweep sw;
+  sw.h = h; sw.who = who; sw.n_scen = n_scen; sw.first = first; sw.count = count;
+  sw.out_node = out_node; sw.out_counters = out_counters; sw.st = st;
+  return sw;
+}
+
+// ksim_sweep_drain, ksim_sweep_affinity, ksim_sweep_volumes and ksim_sweep_policy: the checks they share that
+// need no device, in their order.  drain (ksim_sweep_drain): the queues must be given; the others check the
+// stale tables and the residents.
+int queue_checks(const Sweep& sw, bool drain) {
+  if (int rc = check_failures(sw.h, sw.who, sw.fail)) return rc;
+  if (int rc = check_queue(sw.h, sw.who, sw.n_scen, sw.rq, drain, sw.first, sw.count, sw.out_node)) return rc;
+  return drain ? KSIM_OK : check_residents(sw.h, sw.who, sw.res);
+}
+
+// ... and, once the entry has set the device, what they share before the general form.  drain: the affinity
+// tables are checked as by ksim_sweep_nodes and out_rehosted is always written; the others write zeros to
+// out_rehosted (may be null) when there are no queues.
+int queue_sweep(Sweep& sw, bool drain) {
+  ksim_handle* h = sw.h;
+  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
+  if (drain)
+    if (int rc0 = ksim_rt_check_aff(h, sw.who)) return rc0;
+  if (!drain && !sw.rq) {
+    if (sw.out_rehosted) std::fill(sw.out_rehosted, sw.out_rehosted + sw.n_scen, 0);
+    sw.out_rehosted = nullptr;
+  }
+  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
+  return sweep_general(sw);
+}
+
 }  // namespace
 
 extern "C" {
@@ -794,73 +863,59 @@ extern "C" {
 int ksim_sweep(ksim_handle* h, const int64_t* weights, int32_t n_scen, int64_t first, int64_t count, int32_t* out_node,
                uint64_t* out_counters, ksim_stats* st) {
   if (!weights) return ksim_fail(h, KSIM_E_INVAL, "ksim_sweep: null argument");
-  return sweep_impl({h, "ksim_sweep", weights, nullptr, n_scen, first, count, out_node, out_counters, nullptr, nullptr, st});
+  Sweep sw = sweep_of(h, "ksim_sweep", n_scen, first, count, out_node, out_counters, st);
+  sw.weights = weights;
+  return sweep_impl(sw);
 }
 
 int ksim_sweep_nodes(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
                      int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled, ksim_stats* st) {
-  return sweep_impl({h, "ksim_sweep_nodes", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
-                     nullptr, st});
+  Sweep sw = sweep_of(h, "ksim_sweep_nodes", n_scen, first, count, out_node, out_counters, st);
+  sw.weights = weights; sw.absent = absent; sw.out_scheduled = out_scheduled;
+  return sweep_impl(sw);
 }
 
 int ksim_sweep_explain(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen, int64_t first,
                        int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
                        const ksim_sweep_failures* fail, ksim_stats* st) {
   if (int rc = check_failures(h, "ksim_sweep_explain", fail)) return rc;
-  return sweep_impl({h, "ksim_sweep_explain", weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled,
-                     fail, st});
+  Sweep sw = sweep_of(h, "ksim_sweep_explain", n_scen, first, count, out_node, out_counters, st);
+  sw.weights = weights; sw.absent = absent; sw.out_scheduled = out_scheduled; sw.fail = fail;
+  return sweep_impl(sw);
 }
 
 int ksim_sweep_drain(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_requeue* rq, int64_t first,
                      int64_t count, int32_t* out_node, uint64_t* out_counters, int32_t* out_scheduled,
                      int32_t* out_rehosted, const ksim_sweep_failures* fail, ksim_stats* st) {
-  const char* who = "ksim_sweep_drain";
-  if (int rc = check_failures(h, who, fail)) return rc;
-  if (int rc = check_queue(h, who, n_scen, rq, true, first, count, out_node)) return rc;
+  Sweep sw = sweep_of(h, "ksim_sweep_drain", n_scen, first, count, out_node, out_counters, st);
+  sw.absent = absent; sw.out_scheduled = out_scheduled; sw.fail = fail; sw.rq = rq; sw.out_rehosted = out_rehosted;
+  if (int rc = queue_checks(sw, true)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (int rc0 = ksim_rt_check_aff(h, who)) return rc0;
-  Sweep sw{h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq, out_rehosted};
-  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
-  return sweep_general(sw);
+  return queue_sweep(sw, true);
 }
 
 int ksim_sweep_affinity(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_residents* res,
                         const ksim_sweep_requeue* rq, int64_t first, int64_t count, int32_t* out_node,
                         uint64_t* out_counters, int32_t* out_scheduled, int32_t* out_rehosted,
                         const ksim_sweep_failures* fail, ksim_stats* st) {
-  const char* who = "ksim_sweep_affinity";
-  if (int rc = check_failures(h, who, fail)) return rc;
-  if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
-  if (int rc = check_residents(h, who, res)) return rc;
+  Sweep sw = sweep_of(h, "ksim_sweep_affinity", n_scen, first, count, out_node, out_counters, st);
+  sw.absent = absent; sw.out_scheduled = out_scheduled; sw.fail = fail; sw.rq = rq; sw.out_rehosted = out_rehosted;
+  sw.res = res; sw.ipa = true;
+  if (int rc = queue_checks(sw, false)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
-  Sweep sw{h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
-           rq ? out_rehosted : nullptr};
-  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
-  sw.ipa = true;
-  sw.res = res;
-  return sweep_general(sw);
+  return queue_sweep(sw, false);
 }
 
 int ksim_sweep_volumes(ksim_handle* h, const uint32_t* absent, int32_t n_scen, const ksim_sweep_residents* res,
                        const ksim_sweep_requeue* rq, int64_t first, int64_t count, int32_t* out_node,
                        uint64_t* out_counters, int32_t* out_scheduled, int32_t* out_rehosted,
                        const ksim_sweep_failures* fail, ksim_stats* st) {
-  const char* who = "ksim_sweep_volumes";
-  if (int rc = check_failures(h, who, fail)) return rc;
-  if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
-  if (int rc = check_residents(h, who, res)) return rc;
+  Sweep sw = sweep_of(h, "ksim_sweep_volumes", n_scen, first, count, out_node, out_counters, st);
+  sw.absent = absent; sw.out_scheduled = out_scheduled; sw.fail = fail; sw.rq = rq; sw.out_rehosted = out_rehosted;
+  sw.res = res; sw.vol = true;
+  if (int rc = queue_checks(sw, false)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
-  Sweep sw{h, who, nullptr, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
-           rq ? out_rehosted : nullptr};
-  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
-  sw.vol = true;
-  sw.res = res;
-  return sweep_general(sw);
+  return queue_sweep(sw, false);
 }
 
 int ksim_sweep_policy(ksim_handle* h, const int64_t* weights, const uint32_t* absent, int32_t n_scen,
@@ -871,9 +926,10 @@ int ksim_sweep_policy(ksim_handle* h, const int64_t* weights, const uint32_t* ab
   if (!weights) return ksim_fail(h, KSIM_E_INVAL, "%s: null argument", who);
   if (outcome && (!outcome->listed || !outcome->used || !outcome->free_cpu || !outcome->free_mem))
     return ksim_fail(h, KSIM_E_INVAL, "%s: an outcome without a listed, used, free_cpu or free_mem array", who);
-  if (int rc = check_failures(h, who, fail)) return rc;
-  if (int rc = check_queue(h, who, n_scen, rq, false, first, count, out_node)) return rc;
-  if (int rc = check_residents(h, who, res)) return rc;
+  Sweep sw = sweep_of(h, who, n_scen, first, count, out_node, out_counters, st);
+  sw.absent = absent; sw.out_scheduled = out_scheduled; sw.fail = fail; sw.rq = rq; sw.out_rehosted = out_rehosted;
+  sw.res = res; sw.pol = true; sw.weights = weights; sw.outcome = outcome;
+  if (int rc = queue_checks(sw, false)) return rc;
   {  // the weight rules, on the host alone
     int32_t s = 0;
     int slot = -1;
@@ -895,16 +951,7 @@ int ksim_sweep_policy(ksim_handle* h, const int64_t* weights, const uint32_t* ab
     }
   }
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->ctx.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
-  if (!rq && out_rehosted) std::fill(out_rehosted, out_rehosted + n_scen, 0);
-  Sweep sw{h, who, weights, absent, n_scen, first, count, out_node, out_counters, out_scheduled, fail, st, rq,
-           rq ? out_rehosted : nullptr};
-  sw.aw = (int32_t)((h->ctx.n + 31) / 32);
-  sw.vol = h->have_vol;  // the VOL instantiations when volume tables are loaded, else the plain, SPR or IPA ones
-  sw.pol = true;
-  sw.res = res;
-  sw.outcome = outcome;
-  return sweep_general(sw);
+  return queue_sweep(sw, false);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass, field
 
@@ -401,6 +402,68 @@ def plan(cluster: Cluster, predicates, priorities, device=0, mode=abi.MODE_AUTO,
     return Plan(cfg, flags, tables, na_add, const_score, pods, affinity, volumes, "NoVolumeZoneConflict" in predicates)
 
 
+def _explained(explain):
+    return explain is not None and explain is not False
+
+
+class SweepBuffers:
+    """The arrays and ctypes structs of one sweep call over S scenarios and count pods, without a handle:
+    out [S][width or count], ctr / sched / rehosted [S], st; weights and absent (absent_mask) as given.
+    requeue (a list of queue indices per scenario): off [S + 1] cumulative from 0, pod back to back, pre
+    parallel to pod (prefix(): per scenario), rq = byref(abi.SweepRequeue).
+    explain (True = the longest prefix + count, or an int cap): fails = dict(count, listed [S], pod [S][cap],
+    hist [S][cap][abi.NREASONS]), pod and hist filled with -1, f = byref(abi.SweepFailures).
+    residents (the cluster's (node rank, aff_ident, aff_class) rows): res = the rows, then one row per bound
+    (queue index, node rank) pair whose pod has an affinity identity or class; rs = abi.SweepResidents.
+    outcome: rec = dict(listed, used [S], free_cpu, free_mem [S][abi.OUTCOME_BUCKETS]), oc = byref of it.
+    What was not asked for is None."""
+    rs = res = rq = off = pod = pre = f = fails = oc = rec = None
+
+    def __init__(self, S, count, weights=None, absent=None, requeue=None, explain=None, residents=None, bound=(),
+                 pods=None, outcome=False, width=None):
+        i32 = C.c_int32
+        self.S = S
+        self.weights = None if weights is None else np.ascontiguousarray(weights, np.int64)
+        self.absent = absent
+        if residents is not None:
+            rows = [np.asarray(residents, np.int32).reshape(-1, 3)]
+            for q, w in bound:
+                p = pods[int(q)]
+                if p["aff_ident"] > 0 or p["aff_class"] > 0:
+                    rows.append(np.array([[int(w), p["aff_ident"], p["aff_class"]]], np.int32))
+            self.res = np.concatenate(rows)
+            self._res_cols = [np.ascontiguousarray(self.res[:, k]) for k in range(3)]
+            self.rs = abi.SweepResidents(len(self.res), *(abi.ptr(c, i32) for c in self._res_cols))
+        if requeue is not None:
+            requeue = [np.asarray(list(r), np.int64).reshape(-1) for r in requeue]
+            self.off = np.zeros(S + 1, np.int64)
+            self.off[1:] = np.cumsum([len(r) for r in requeue])
+            self.pod = np.ascontiguousarray(np.concatenate(requeue)) if S and self.off[-1] else np.zeros(0, np.int64)
+            self.pre = np.zeros(len(self.pod), np.int32)
+            self._rq = abi.SweepRequeue(abi.ptr(self.off, C.c_int64), abi.ptr(self.pod, C.c_int64), abi.ptr(self.pre, i32))
+            self.rq = C.byref(self._rq)
+        self.out = np.zeros((S, count if width is None else width), np.int32)
+        self.ctr, self.sched, self.rehosted = np.zeros(S, np.uint64), np.zeros(S, np.int32), np.zeros(S, np.int32)
+        if _explained(explain):
+            longest = int(np.diff(self.off).max()) if self.off is not None and S else 0
+            cap = longest + count if explain is True else int(explain)
+            self.fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
+                              pod=np.full((S, max(cap, 0)), -1, np.int32),
+                              hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
+            self._f = abi.SweepFailures(cap, *(abi.ptr(self.fails[k], i32) for k in ("count", "listed", "pod", "hist")))
+            self.f = C.byref(self._f)
+        if outcome:
+            self.rec = dict(listed=np.zeros(S, np.int32), used=np.zeros(S, np.int32),
+                            free_cpu=np.zeros((S, abi.OUTCOME_BUCKETS), np.int32),
+                            free_mem=np.zeros((S, abi.OUTCOME_BUCKETS), np.int32))
+            self._oc = abi.SweepOutcome(*(abi.ptr(self.rec[k], i32) for k in ("listed", "used", "free_cpu", "free_mem")))
+            self.oc = C.byref(self._oc)
+        self.st = abi.Stats()
+
+    def prefix(self):
+        return [self.pre[self.off[k]:self.off[k + 1]] for k in range(self.S)]
+
+
 class GenericScheduler:
     """Batch drop-in for genericScheduler + Scheduler.assume on one MI355X.  label_presence:
     (labels, presence) of a Policy's CheckNodeLabelPresence predicate (policy.key_sets)."""
@@ -521,22 +584,11 @@ class GenericScheduler:
         absent, with and without scenario weights, in every form."""
         n = len(self._pods)
         count = n - first if count is None else count
-        if explain is not None and explain is not False:
-            return self._sweep_explain(scenarios, first, count, absent, count if explain is True else int(explain))
-        if absent is not None:
-            return self._sweep_nodes(scenarios, first, count, absent)
-        w = np.zeros((len(scenarios), abi.NW), np.int64)
-        for k, pri in enumerate(scenarios):
-            cfg = make_config(self.predicates, pri)
-            if cfg.no_priorities != self.cfg.no_priorities:
-                raise Unsupported("a sweep scenario needs a non-empty prioritizer list like the scheduler's")
-            w[k] = list(cfg.weights)
-        out = np.zeros((len(scenarios), count), np.int32)
-        ctr = np.zeros(len(scenarios), np.uint64)
-        st = abi.Stats()
-        self.h.call("ksim_sweep", abi.vptr(w), len(scenarios), first, count, abi.vptr(out), abi.vptr(ctr), C.byref(st))
-        self.last_stats = st
-        return out, ctr, st
+        if _explained(explain) or absent is not None:
+            return self._sweep_sets(scenarios, first, count, absent, explain)
+        b = SweepBuffers(len(scenarios), count, weights=self._sweep_weights(scenarios))
+        self.h.call("ksim_sweep", abi.vptr(b.weights), b.S, first, count, abi.vptr(b.out), abi.vptr(b.ctr), C.byref(b.st))
+        return self._swept(b, scheduled=False)
 
     def _sweep_weights(self, scenarios):
         w = np.zeros((len(scenarios), abi.NW), np.int64)
@@ -547,7 +599,22 @@ class GenericScheduler:
             w[k] = list(cfg.weights)
         return w
 
-    def _sweep_explain(self, scenarios, first, count, absent, cap):
+    def _swept(self, b, scheduled=True):
+        """After a sweep call over the buffers b: the last_* attributes and the return value."""
+        self.last_stats = b.st
+        if scheduled:
+            self.last_scheduled = b.sched
+        if b.fails is not None:
+            self.last_failures = b.fails
+        if b.rec is not None:
+            self.last_outcome = b.rec
+        if b.rq is None:
+            return b.out, b.ctr, b.st
+        self.last_rehosted = b.rehosted
+        return b.out, b.prefix(), b.ctr, b.st
+
+    def _sweep_sets(self, scenarios, first, count, absent, explain):
+        """sweep with node sets (ksim_sweep_nodes), with records (ksim_sweep_explain), or both."""
         mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
         if mask is None and scenarios is None:
             raise abi.KsimError(abi.E_INVAL, "sweep: neither scenarios nor absent sets")
@@ -555,39 +622,13 @@ class GenericScheduler:
         if scenarios is not None and len(scenarios) != S:
             raise abi.KsimError(abi.E_INVAL, "sweep: %d scenarios but %d absent sets" % (len(scenarios), S))
         w = None if scenarios is None else self._sweep_weights(scenarios)
-        out = np.zeros((S, count), np.int32)
-        ctr = np.zeros(S, np.uint64)
-        bound = np.zeros(S, np.int32)
-        fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
-                     pod=np.full((S, max(cap, 0)), -1, np.int32),
-                     hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
-        f = abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
-                              abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32))
-        st = abi.Stats()
-        self.h.call("ksim_sweep_explain", abi.vptr(w), abi.vptr(mask), S, first, count, abi.vptr(out), abi.vptr(ctr),
-                    abi.vptr(bound), C.byref(f), C.byref(st))
-        self.last_stats = st
-        self.last_scheduled = bound
-        self.last_failures = fails
-        return out, ctr, st
-
-    def _sweep_nodes(self, scenarios, first, count, absent):
-        mask = absent_mask(self.cluster.n_nodes, absent)
-        S = len(mask)
-        w = None
-        if scenarios is not None:
-            if len(scenarios) != S:
-                raise abi.KsimError(abi.E_INVAL, "sweep: %d scenarios but %d absent sets" % (len(scenarios), S))
-            w = self._sweep_weights(scenarios)
-        out = np.zeros((S, count), np.int32)
-        ctr = np.zeros(S, np.uint64)
-        bound = np.zeros(S, np.int32)
-        st = abi.Stats()
-        self.h.call("ksim_sweep_nodes", abi.vptr(w), abi.vptr(mask), S, first, count, abi.vptr(out), abi.vptr(ctr),
-                    abi.vptr(bound), C.byref(st))
-        self.last_stats = st
-        self.last_scheduled = bound
-        return out, ctr, st
+        b = SweepBuffers(S, count, weights=w, absent=mask, explain=explain)
+        args = (abi.vptr(b.weights), abi.vptr(mask), S, first, count, abi.vptr(b.out), abi.vptr(b.ctr), abi.vptr(b.sched))
+        if b.f is None:
+            self.h.call("ksim_sweep_nodes", *args, C.byref(b.st))
+        else:
+            self.h.call("ksim_sweep_explain", *args, b.f, C.byref(b.st))
+        return self._swept(b)
 
     def sweep_drain(self, absent, requeue, first=0, count=None, explain=None):
         """Drain what-if (ksim_sweep_drain, include/ksim_drain.h): sweep(None, absent=...) with a
@@ -605,40 +646,7 @@ class GenericScheduler:
         explain: as in sweep; self.last_failures["pod"] then holds positions in the scenario's own
         queue (0 .. len(requeue[s])-1 the prefix, len(requeue[s]) + i range pod first + i) and
         count the failed pods of prefix and range together."""
-        n = len(self._pods)
-        count = n - first if count is None else count
-        requeue = [np.asarray(list(r), np.int64).reshape(-1) for r in requeue]
-        S = len(requeue)
-        mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
-        if mask is not None and len(mask) != S:
-            raise abi.KsimError(abi.E_INVAL, "sweep_drain: %d re-queue lists but %d absent sets" % (S, len(mask)))
-        off = np.zeros(S + 1, np.int64)
-        off[1:] = np.cumsum([len(r) for r in requeue])
-        pod = np.ascontiguousarray(np.concatenate(requeue)) if S and off[-1] else np.zeros(0, np.int64)
-        pre = np.zeros(len(pod), np.int32)
-        rq = abi.SweepRequeue(abi.ptr(off, C.c_int64), abi.ptr(pod, C.c_int64), abi.ptr(pre, C.c_int32))
-        out = np.zeros((S, max(count, 0)), np.int32)
-        ctr = np.zeros(S, np.uint64)
-        bound = np.zeros(S, np.int32)
-        rehosted = np.zeros(S, np.int32)
-        f = fails = None
-        if explain is not None and explain is not False:
-            longest = int(np.diff(off).max()) if S else 0
-            cap = longest + count if explain is True else int(explain)
-            fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
-                         pod=np.full((S, max(cap, 0)), -1, np.int32),
-                         hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
-            f = C.byref(abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
-                                          abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32)))
-        st = abi.Stats()
-        self.h.call("ksim_sweep_drain", abi.vptr(mask), S, C.byref(rq), first, count, abi.vptr(out), abi.vptr(ctr),
-                    abi.vptr(bound), abi.vptr(rehosted), f, C.byref(st))
-        self.last_stats = st
-        self.last_scheduled = bound
-        self.last_rehosted = rehosted
-        if fails is not None:
-            self.last_failures = fails
-        return out, [pre[off[k]:off[k + 1]] for k in range(S)], ctr, st
+        return self._sweep_owned("sweep_drain", "ksim_sweep_drain", absent, list(requeue), first, count, explain, None)
 
     def has_affinity_terms(self):
         """The loaded affinity tables hold an inter-pod affinity term — required, preferred or carried —
@@ -706,8 +714,9 @@ class GenericScheduler:
                                  weights=w, outcome=outcome)
 
     def _sweep_owned(self, who, entry, absent, requeue, first, count, explain, bound, weights=None, outcome=False):
-        """sweep_affinity / sweep_volumes / sweep_policy: the entries whose scenarios own affinity or
-        volume state.  weights (sweep_policy): the scenarios' rows, which then give the scenario count."""
+        """sweep_drain / sweep_affinity / sweep_volumes / sweep_policy: the entries that take prefix queues.
+        bound None (sweep_drain): the entry takes no residents.  weights (sweep_policy): the scenarios' rows,
+        which then give the scenario count."""
         n = len(self._pods)
         count = n - first if count is None else count
         mask = None if absent is None else absent_mask(self.cluster.n_nodes, absent)
@@ -718,59 +727,16 @@ class GenericScheduler:
             raise abi.KsimError(abi.E_INVAL, "%s: %d scenarios but %d re-queue lists" % (who, S, len(requeue)))
         if mask is not None and len(mask) != S:
             raise abi.KsimError(abi.E_INVAL, "%s: %d re-queue lists but %d absent sets" % (who, S, len(mask)))
-        res = [np.asarray(self.cluster.residents, np.int32).reshape(-1, 3)]
-        for q, w in bound:
-            p = self._pods[int(q)]
-            if p["aff_ident"] > 0 or p["aff_class"] > 0:
-                res.append(np.array([[int(w), p["aff_ident"], p["aff_class"]]], np.int32))
-        res = np.concatenate(res)
-        cols = [np.ascontiguousarray(res[:, k]) for k in range(3)]
-        rs = abi.SweepResidents(len(res), *(abi.ptr(c, C.c_int32) for c in cols))
-        rq = pre = off = None
-        if requeue is not None:
-            requeue = [np.asarray(list(r), np.int64).reshape(-1) for r in requeue]
-            off = np.zeros(S + 1, np.int64)
-            off[1:] = np.cumsum([len(r) for r in requeue])
-            pod = np.ascontiguousarray(np.concatenate(requeue)) if S and off[-1] else np.zeros(0, np.int64)
-            pre = np.zeros(len(pod), np.int32)
-            rq = C.byref(abi.SweepRequeue(abi.ptr(off, C.c_int64), abi.ptr(pod, C.c_int64), abi.ptr(pre, C.c_int32)))
-        out = np.zeros((S, max(count, 0)), np.int32)
-        ctr = np.zeros(S, np.uint64)
-        sched = np.zeros(S, np.int32)
-        rehosted = np.zeros(S, np.int32)
-        f = fails = None
-        if explain is not None and explain is not False:
-            longest = int(np.diff(off).max()) if off is not None and S else 0
-            cap = longest + count if explain is True else int(explain)
-            fails = dict(count=np.zeros(S, np.int32), listed=np.zeros(S, np.int32),
-                         pod=np.full((S, max(cap, 0)), -1, np.int32),
-                         hist=np.full((S, max(cap, 0), abi.NREASONS), -1, np.int32))
-            f = C.byref(abi.SweepFailures(cap, abi.ptr(fails["count"], C.c_int32), abi.ptr(fails["listed"], C.c_int32),
-                                          abi.ptr(fails["pod"], C.c_int32), abi.ptr(fails["hist"], C.c_int32)))
-        st = abi.Stats()
+        b = SweepBuffers(S, count, weights=weights, absent=mask, requeue=requeue, explain=explain, width=max(count, 0),
+                         residents=None if bound is None else self.cluster.residents, bound=bound, pods=self._pods,
+                         outcome=outcome and weights is not None)
+        args = (abi.vptr(mask), S, *(() if b.rs is None else (C.byref(b.rs),)), b.rq, first, count, abi.vptr(b.out),
+                abi.vptr(b.ctr), abi.vptr(b.sched), abi.vptr(b.rehosted), b.f)
         if weights is None:
-            self.h.call(entry, abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out), abi.vptr(ctr),
-                        abi.vptr(sched), abi.vptr(rehosted), f, C.byref(st))
+            self.h.call(entry, *args, C.byref(b.st))
         else:
-            oc = rec = None
-            if outcome:
-                rec = dict(listed=np.zeros(S, np.int32), used=np.zeros(S, np.int32),
-                           free_cpu=np.zeros((S, abi.OUTCOME_BUCKETS), np.int32),
-                           free_mem=np.zeros((S, abi.OUTCOME_BUCKETS), np.int32))
-                oc = C.byref(abi.SweepOutcome(*(abi.ptr(rec[k], C.c_int32) for k in ("listed", "used", "free_cpu", "free_mem"))))
-            weights = np.ascontiguousarray(weights, np.int64)
-            self.h.call(entry, abi.vptr(weights), abi.vptr(mask), S, C.byref(rs), rq, first, count, abi.vptr(out),
-                        abi.vptr(ctr), abi.vptr(sched), abi.vptr(rehosted), f, oc, C.byref(st))
-            if rec is not None:
-                self.last_outcome = rec
-        self.last_stats = st
-        self.last_scheduled = sched
-        if fails is not None:
-            self.last_failures = fails
-        if requeue is None:
-            return out, ctr, st
-        self.last_rehosted = rehosted
-        return out, [pre[off[k]:off[k + 1]] for k in range(S)], ctr, st
+            self.h.call(entry, abi.vptr(b.weights), *args, b.oc, C.byref(b.st))
+        return self._swept(b)
 
     def evaluate(self, pod):
         """Per-node (fit, reason mask, map score, reduce class) for one loaded pod (no commit)."""
@@ -1072,6 +1038,25 @@ class Report:
         return review_text(self.review)
 
 
+def _placements(cluster, pod_names, row):
+    """[(pod name, node name or None)] of a what-if record: row holds a node rank or -1 per pod."""
+    names = cluster.names
+    return [(pn, names[w] if w >= 0 else None) for pn, w in zip(pod_names, row)]
+
+
+def _fit_errors(cluster, fails, s, pod_name):
+    """listed, explained and fit_errors of scenario s's what-if record from a sweep's last_failures;
+    pod_name maps a record's position in the scenario's queue to the pod's name."""
+    from .report import ERR_NO_NODES
+    listed = int(fails["listed"][s])
+    kept = min(int(fails["count"][s]), fails["pod"].shape[1])
+    scal = cluster.scalar_names.items
+    return dict(listed=listed, explained=kept, fit_errors=[
+        (pod_name(int(fails["pod"][s, k])),
+         fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
+        for k in range(kept)])
+
+
 class ClusterCapacity:
     """The simulator (pkg/scheduler/simulator.go:286-342 New, :187-213 Run): nodes and running
     pods of a snapshot, the simulation pods popped LIFO from the expanded podspec list
@@ -1143,6 +1128,16 @@ class ClusterCapacity:
         rep.review = get_report(rep.status)
         return rep
 
+    @contextlib.contextmanager
+    def _own_scheduler(self, cluster):
+        """A scheduler of its own over cluster for one what-if sweep, closed afterwards."""
+        predicates, priorities, kw = self._sched_args
+        g = GenericScheduler(cluster, predicates, priorities, collect_reasons=False, **kw)
+        try:
+            yield g
+        finally:
+            g.close()
+
     def _outage_ranks(self, outages):
         """The sorted node ranks of every (name, node names or indices) outage."""
         cl = self.cluster
@@ -1188,9 +1183,7 @@ class ClusterCapacity:
         sets_ = self._outage_ranks(outages)
         if not outages:
             return []
-        predicates, priorities, kw = self._sched_args
-        g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
-        try:
+        with self._own_scheduler(cl) as g:
             if g.volumes is not None:  # volume tables: every outage owns its mounts (and its affinity state)
                 out, _, _ = g.sweep_volumes(sets_, None, first, count, explain=explain if explain else None)
             elif g.has_affinity_terms():  # inter-pod affinity terms: every outage owns its affinity state
@@ -1198,24 +1191,14 @@ class ClusterCapacity:
             else:
                 out, _, _ = g.sweep(None, first, count, absent=sets_, explain=explain if explain else None)
             fails = g.last_failures if explain else None
-        finally:
-            g.close()
-        names = cl.names
         pod_names = cl.pod_names[first:first + out.shape[1]]
         recs = []
         for s, ((name, _), idx, row) in enumerate(zip(outages, sets_, out)):
             bound = int((row >= 0).sum())
             recs.append(dict(name=name, absent=len(idx), scheduled=bound, failed=len(row) - bound,
-                             placements=[(pn, names[w] if w >= 0 else None) for pn, w in zip(pod_names, row)]))
+                             placements=_placements(cl, pod_names, row)))
             if fails is not None:
-                from .report import ERR_NO_NODES
-                listed = int(fails["listed"][s])
-                kept = min(int(fails["count"][s]), fails["pod"].shape[1])
-                scal = cl.scalar_names.items
-                recs[-1].update(listed=listed, explained=kept, fit_errors=[
-                    (pod_names[int(fails["pod"][s, k])],
-                     fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
-                    for k in range(kept)])
+                recs[-1].update(_fit_errors(cl, fails, s, lambda k: pod_names[k]))
         return recs
 
     def policy_what_if(self, policies, outages=None, first=0, count=None, explain=False):
@@ -1242,33 +1225,21 @@ class ClusterCapacity:
         sets_ = None if outages is None else self._outage_ranks(outages)
         cases = [(pn, pri, None, None) for pn, pri in policies] if outages is None else \
             [(pn, pri, on, idx) for pn, pri in policies for (on, _), idx in zip(outages, sets_)]
-        predicates, priorities, kw = self._sched_args
-        g = GenericScheduler(cl, predicates, priorities, collect_reasons=False, **kw)
-        try:
+        with self._own_scheduler(cl) as g:
             out, _, _ = g.sweep_policy([c[1] for c in cases], None if outages is None else [c[3] for c in cases],
                                        None, first, count, explain=explain if explain else None, outcome=True)
             fails = g.last_failures if explain else None
             oc = g.last_outcome
-        finally:
-            g.close()
-        names = cl.names
         pod_names = cl.pod_names[first:first + out.shape[1]]
         recs = []
         for s, ((pn, _, on, idx), row) in enumerate(zip(cases, out)):
             bound = int((row >= 0).sum())
             recs.append(dict(policy=pn, name=on, absent=len(idx or ()), scheduled=bound, failed=len(row) - bound,
-                             placements=[(q, names[w] if w >= 0 else None) for q, w in zip(pod_names, row)],
+                             placements=_placements(cl, pod_names, row),
                              listed=int(oc["listed"][s]), used=int(oc["used"][s]),
                              free_cpu=[int(v) for v in oc["free_cpu"][s]], free_mem=[int(v) for v in oc["free_mem"][s]]))
-            if fails is not None:
-                from .report import ERR_NO_NODES
-                listed = int(fails["listed"][s])
-                kept = min(int(fails["count"][s]), fails["pod"].shape[1])
-                scal = cl.scalar_names.items
-                recs[-1].update(explained=kept, fit_errors=[
-                    (pod_names[int(fails["pod"][s, k])],
-                     fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
-                    for k in range(kept)])
+            if fails is not None:  # (listed stays the outcome's)
+                recs[-1].update((k, v) for k, v in _fit_errors(cl, fails, s, lambda k: pod_names[k]).items() if k != "listed")
         return recs
 
     def drain_what_if(self, outages, first=0, count=None, explain=False, evictable=None):
@@ -1310,33 +1281,20 @@ class ClusterCapacity:
         copies = [requeue_copy(pod) for _, pod in evicted]
         dcl = Cluster.from_objects(self.nodes, self.running, self.order + copies, **self._cluster_args)
         requeue = [[nq + k for k, (node, _) in enumerate(evicted) if node in set(idx)] for idx in sets_]
-        predicates, priorities, kw = self._sched_args
-        g = GenericScheduler(dcl, predicates, priorities, collect_reasons=False, **kw)
-        try:
+        with self._own_scheduler(dcl) as g:
             drain = (g.sweep_volumes if g.volumes is not None else
                      g.sweep_affinity if g.has_affinity_terms() else g.sweep_drain)
             out, pre, _, _ = drain(sets_, requeue, first, count, explain=explain if explain else None)
             fails = g.last_failures if explain else None
-        finally:
-            g.close()
-        names = dcl.names
         pod_names = dcl.pod_names
         recs = []
         for s, ((name, _), idx, row, rq, got) in enumerate(zip(outages, sets_, out, requeue, pre)):
             bound, back = int((row >= 0).sum()), int((got >= 0).sum())
             recs.append(dict(name=name, absent=len(idx), evicted=len(rq), rehosted=back, stranded=len(rq) - back,
-                             requeued=[(pod_names[q], names[w] if w >= 0 else None) for q, w in zip(rq, got)],
+                             requeued=_placements(dcl, [pod_names[q] for q in rq], got),
                              scheduled=bound, failed=len(row) - bound,
-                             placements=[(pn, names[w] if w >= 0 else None)
-                                         for pn, w in zip(pod_names[first:first + len(row)], row)]))
+                             placements=_placements(dcl, pod_names[first:first + len(row)], row)))
             if fails is not None:
-                from .report import ERR_NO_NODES
-                listed = int(fails["listed"][s])
-                kept = min(int(fails["count"][s]), fails["pod"].shape[1])
-                scal = dcl.scalar_names.items
                 queue = list(rq) + list(range(first, first + len(row)))  # the outage's own queue, by loaded index
-                recs[-1].update(listed=listed, explained=kept, fit_errors=[
-                    (pod_names[queue[int(fails["pod"][s, k])]],
-                     fit_error_message(listed, fails["hist"][s, k], scal) if listed else ERR_NO_NODES)
-                    for k in range(kept)])
+                recs[-1].update(_fit_errors(dcl, fails, s, lambda k: pod_names[queue[k]]))
         return recs
