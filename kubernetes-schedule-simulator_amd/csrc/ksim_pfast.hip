@@ -31,9 +31,44 @@
 // Cached form (CACHE): every (tree class, row) evaluation stays in LDS and only the committed
 // row is re-evaluated.  Its histogram sub-form (HIST, scores <= 63): per class the number of
 // rows at each score (ksim_phist.h), so a pod's (fit count, maximum, count at the maximum) is
-// one histogram row read lane = score instead of a scan of the class's column, the owner's
-// fix is that row with two buckets adjusted, and what the owner needs of pod + 1 is read
-// before the sweep and the first barrier.  The exchange itself is the same in every form.
+// one histogram row read lane = score instead of a scan of the class's column.  The exchange
+// itself is the same in every form.
+//
+// HIST, the owner's fix: the row waves prepare it.  In the iteration of pod p they read pod
+// p + 1's histogram row once (hist_publish: F, the top bucket M and its count, the next
+// non-empty bucket below and its count) and, for every row j pod p can commit to (the rows at
+// the workgroup's maximum of p), the lane that owns j evaluates p + 1 against "row + p", takes
+// the row's cached evaluation for p + 1's class, and writes the finished 8-byte fix granule —
+// tag of p + 1, (F', C', M') from khist::fix, the 2^48 stop bit — to fixg[j].  Each row wave then
+// releases its LDS writes and stores the iteration's number (pods of this call so far + 1) in
+// its own word s_done[w].  The owner, once it has decided p and turned its rank into a row,
+// waits until the word of the wave that owns that row shows this iteration (normally it did
+// long before; one word per wave, not one count of all seven, because the owner needs one
+// wave's granule and the slowest wave finishes about when the owner arrives: measured, DESIGN.md
+// §4), reads fixg[jsel] and stores it, before the main barrier.  Its tail
+// after the barrier (commit, every class's re-evaluation, one count moved per class, s_wg and
+// s_bm of p + 1) takes what it needs from that granule and is off the chain.
+//  * Exchange unchanged: granule format, tags, NSLOT, replicas, what the sweep tests and which
+//    wave stores what are as before; only the moment of the owner's store moved, from after its
+//    main barrier to before it, still after its own decision of p.  The slot it overwrites,
+//    (p + 1) mod NSLOT, held p - 3's fix.  A workgroup reads that only in its sweep of p - 3.
+//    The owner decides p only after every workgroup's granule of p is there; a workgroup's row
+//    waves publish p in iteration p - 1, which its control wave entered after its sweeps of
+//    p - 3 and p - 2: every workgroup has consumed p - 3's fix before any can decide p.
+//  * fixg[j]'s inputs are stable while it is computed and read: p + 1's histogram row, its
+//    cache column, the rows and s_wg[p & 1][1] are written only by an owner's tail, between the
+//    main barrier and the barrier after it, never between an iteration's start and its main
+//    barrier.  (The commit to the row stays after the main barrier for that reason.)
+//  * One fixg buffer suffices: written by the row waves in iteration p before its main barrier,
+//    read by the owner before the same barrier (after s_done, with an acquire), rewritten only
+//    by iteration p + 1, beyond that barrier.  It overlays ev / ev2 of the uncached form, which
+//    the cached forms never read; the LDS sizes and the form boundaries do not move.
+//  * No deadlock: a row wave reaches its store to s_done without waiting for anything the
+//    control wave does in that iteration, so the owner's wait ends although it stands before
+//    the main barrier.  s_done is zeroed when a call starts and only grows; the owner compares
+//    it with the iteration's number in wrap-safe unsigned arithmetic.  The wait is bounded like
+//    every spin here: an owner that gives up sets the error word and mode -1 and stores nothing,
+//    and the other workgroups leave through the sweep's time limit.
 #include <algorithm>
 
 #include "ksim_decide.h"
@@ -189,6 +224,7 @@ struct FRows {  // LDS image of the owned rows (SoA)
   uint32_t* rma;  // STREAM: [2][chunk] reason mask of ev (registers in the LDS form)
   int16_t* cache; // CACHE: [ncls][chunk] evaluation of tree class k on row j as it stands
   uint16_t* hist; // HIST: [ncls][64] rows of the workgroup at each score of class k (ksim_phist.h)
+  uint64_t* fixg; // HIST: [chunk] the fix granule of pod p+1 if pod p commits to row j (over ev .. top_list)
 };
 
 constexpr int LDS_ROW_BYTES = 8 * 8 + 8 * 4;  // 96: 8 float64 + allowed, count, flags, ev[2], ev2, rm2, top_list
@@ -216,6 +252,7 @@ __device__ __forceinline__ FRows carve(int rows, const PfArgs& a, int64_t lo) {
     r.rma = r.rm2 + 2 * rows;  // after top_list
     r.cache = nullptr;
     r.hist = nullptr;
+    r.fixg = nullptr;
     return r;
   }
   double* d = reinterpret_cast<double*>(kf_smem);
@@ -227,6 +264,9 @@ __device__ __forceinline__ FRows carve(int rows, const PfArgs& a, int64_t lo) {
   r.ev = q + 3 * rows;
   r.ev2 = q + 5 * rows;
   r.rm2 = reinterpret_cast<uint32_t*>(q + 6 * rows);
+  // HIST: 8 B per row from ev on (20 B per row up to the cache, none of it read in the cached
+  // forms); q is 8-byte aligned, q + 3 rows only for an even row count
+  r.fixg = reinterpret_cast<uint64_t*>(q + 3 * rows + (rows & 1));
   r.cache = reinterpret_cast<int16_t*>(q + 8 * rows);  // after top_list (q + 7 rows)
   r.hist = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(r.cache) + (((size_t)a.ncls * rows * 2 + 15) & ~(size_t)15));
   return r;
@@ -287,6 +327,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
   __shared__ int32_t s_hist[KSIM_NREASONS];
   __shared__ int32_t s_mode[2], s_own[2];     // by pod parity: read after the barrier, rewritten two pods later
   __shared__ int32_t s_arr;
+  __shared__ uint32_t s_done[HIST ? RW : 1];  // HIST, per row wave: iterations of this call whose fix granules it has finished
   // STREAM: commit of pod p deferred to the row waves of the next iteration (by pod parity):
   // row (-1 none) and the AddPod deltas (add cpu, add mem, non-zero cpu, non-zero mem)
   __shared__ int32_t s_prow[2];
@@ -351,6 +392,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
   }
   if (CACHE)
     for (int k = tid; k < a.ncls; k += BS) s_tcl[k] = a.tclass[k];
+  if (HIST && tid < RW) s_done[tid] = 0;
   if (tid == 0) { s_fix[a.first & 1][0] = -1; s_arr = 0; s_prow[0] = s_prow[1] = -1; }
   uint64_t counter = *a.counter;  // replicated genericScheduler.lastNodeIndex
   __syncthreads();
@@ -436,13 +478,14 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
   // M its highest non-empty bucket, C that bucket.  Wave 1 publishes them (the stores of
   // arrive_publish); every wave then leaves the masks of its rows at M — the workgroup's
   // maximum, not the wave's — for seg_prepare.  No wave waits for another.
-  auto hist_publish = [&](int64_t p, int buf) {
+  auto hist_publish = [&](int64_t p, int buf) -> Top2 {
     const int cls = s_pcls[p % RING];
     const int32_t h = R.hist[cls * KSIM_PHIST_BUCKETS + lane];
-    const int32_t M = khist::top(__ballot(h != 0));
+    const uint64_t ne = __ballot(h != 0);
+    const int32_t M = khist::top(ne);
+    const int32_t F = ksimw::sum_i32(h);
+    const int32_t C = __builtin_amdgcn_readlane(h, M < 0 ? 0 : M);  // (an empty row: bucket 0 holds 0)
     if (wv == 1) {
-      const int32_t F = ksimw::sum_i32(h);
-      const int32_t C = __builtin_amdgcn_readlane(h, M < 0 ? 0 : M);  // (an empty row: bucket 0 holds 0)
       if (lane == 0) {
         s_wg[buf][0] = F; s_wg[buf][1] = M; s_wg[buf][2] = C;
         if (NR == 1) ksimx::store_agent((gu64*)spec_at(granules, (int)(p % NSLOT), me), gpack(ptag(p), F, C, M));
@@ -457,6 +500,10 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       const uint64_t bm = __ballot(M >= 0 && j < nrows && (int32_t)c1[j] == M);
       if (lane == 0) s_bm[buf][k][wv - 1] = bm;
     }
+    // the top two buckets, for the fix granules (khist::fix): the second is the highest
+    // non-empty bucket below M
+    const int32_t M2 = khist::top(M < 0 ? 0ull : ne & ~(1ull << M));
+    return Top2{F, M, C, M2, M2 < 0 ? 0 : __builtin_amdgcn_readlane(h, M2 < 0 ? 0 : M2)};
   };
   // LDS form, control wave: the 64-row segments holding rows at the workgroup maximum of the pod in `buf`
   // (lane t = t-th segment from the top: its bitmask, count, and the matches in segments above
@@ -544,7 +591,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       }
     }
     if constexpr (HIST) {
-      hist_publish(a.first, (int)(a.first & 1));
+      (void)hist_publish(a.first, (int)(a.first & 1));
     } else {
       wave_stats(e, (int)(a.first & 1), wv);
       arrive_publish(a.first, (int)(a.first & 1));
@@ -570,9 +617,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
     int32_t e_new = -1;     // STREAM: pod + 1 against the row after pod's commit
     uint32_t m_new = 0;
     int32_t hM_old = -1, hM_new = -1;  // HIST, owner: the workgroup's maximum of pod + 1 before / after the fix
-    int32_t hcls = 0, hrow = 0, hF0 = 0;  // HIST, control wave: pod + 1's class, its histogram row (lane = score), its F
-    int32_t he_old = -1;                  // HIST, owner: the committed row's cached evaluation for that class
-    double hdel[4] = {0.0, 0.0, 0.0, 0.0};  // HIST, control wave: pod's AddPod deltas
+    uint64_t hfix = 0;                 // HIST, owner: the fix granule it stored (fixg[jsel])
 #ifdef KSIM_STAMPS
     uint64_t o_prev = 0;
 #endif
@@ -581,18 +626,6 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       Segs sg{};
       if (STREAM) build_top_list(pb);
       else sg = seg_prepare(pb);
-      if constexpr (HIST) {
-        // what an owner needs of pod + 1 and of pod's deltas, read while the sweep waits anyway:
-        // the class's histogram row (nothing moves a count before the owner's fix) and its F and M
-        if (has_next) {
-          hcls = s_pcls[(pod + 1) % RING];
-          hrow = R.hist[hcls * KSIM_PHIST_BUCKETS + lane];
-          hF0 = ksimw::sum_i32(hrow);
-          hM_old = khist::top(__ballot(hrow != 0));
-        }
-        const ksim_pod& Pp = s_pod[pod % RING];
-        hdel[0] = (double)Pp.add_cpu; hdel[1] = (double)Pp.add_mem; hdel[2] = (double)Pp.nz_cpu; hdel[3] = (double)Pp.nz_mem;
-      }
       STAMP(1);
       // ---------------- a. sweep: every workgroup's granule of pod (+ the owner's fix) -------
       const uint64_t tag = ptag(pod);
@@ -717,11 +750,38 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           mode = -1;
           if (lane == 0) atomicOr(a.err, 2);
         } else if (HIST) {
-          // the four sums at once (no short-circuit: one round of LDS reads), the deltas converted
-          // before the sweep; and the row's evaluation for pod + 1's class, which no row wave writes
-          const double s0 = R.rc[jsel] + hdel[0], s1 = R.rm[jsel] + hdel[1], s2 = R.zc[jsel] + hdel[2], s3 = R.zm[jsel] + hdel[3];
-          if (has_next) he_old = (int32_t)R.cache[hcls * chunk + jsel];
-          stopbit = ((s0 >= EXACT_LIM) | (s1 >= EXACT_LIM) | (s2 >= EXACT_LIM) | (s3 >= EXACT_LIM)) ? (1ull << 55) : 0ull;
+          OSTAMP(22);
+          if (has_next) {
+            // the row waves left pod + 1's finished fix granule for every row pod can commit to:
+            // wait until the wave that owns this row has marked this iteration done (it does so
+            // without waiting for this wave, and usually long ago), then read the granule and store it
+            const uint32_t need = (uint32_t)(pod - a.first + 1);
+            auto short_of = [&]() -> bool {
+              const uint32_t d = __hip_atomic_load(&s_done[(jsel % RT) / 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              return (int32_t)((uint32_t)__builtin_amdgcn_readfirstlane((int32_t)d) - need) < 0;
+            };
+            bool done = true;
+            if (short_of()) {  // (the clock is read only here)
+              OSTAMP(18);
+              const uint64_t tw0 = __builtin_amdgcn_s_memrealtime();
+              do {
+                if (__builtin_amdgcn_s_memrealtime() - tw0 > SPIN_LIMIT_TICKS) { done = false; break; }
+                __builtin_amdgcn_s_sleep(1);
+              } while (short_of());
+              OSTAMP(12);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            if (!done) {  // the peers leave through the sweep's time limit
+              jsel = -1;
+              mode = -1;
+              if (lane == 0) atomicOr(a.err, 2);
+            } else {
+              hfix = R.fixg[jsel];
+              if (NR > 1 && lane < NR) ksimx::store_agent((gu64*)fix_at(granules + lane * REP_STRIDE, (int)((pod + 1) % NSLOT)), hfix);
+              if (NR == 1 && lane == 0) ksimx::store_agent((gu64*)fix_at(granules, (int)((pod + 1) % NSLOT)), hfix);
+            }
+          }
+          OSTAMP(18);
         } else if (!STREAM) {
           const ksim_pod& Pp = s_pod[pod % RING];
           stopbit = (R.rc[jsel] + (double)Pp.add_cpu >= EXACT_LIM || R.rm[jsel] + (double)Pp.add_mem >= EXACT_LIM ||
@@ -739,7 +799,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
             stopbit = (r2.rc >= EXACT_LIM || r2.rm >= EXACT_LIM || r2.zc >= EXACT_LIM || r2.zm >= EXACT_LIM) ? (1ull << 55) : 0ull;
           }
         }
-        OSTAMP(22);
+        if (!HIST) OSTAMP(22);
       }
       if ((mode == 0 || mode == 3) && me == 0 && lane == 0) a.out_node[pod] = mode == 0 ? -1 : -2;
       if (lane == 0) {
@@ -808,11 +868,12 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
         // cached form: pod + 1's statistics are its class's cached evaluations (the rows as they
         // stand), then pod + 1 against "row + pod" only for the rows pod can commit to — the
         // rows at this workgroup's maximum of pod (its owner picks one of them)
+        Top2 ht{};
         if constexpr (HIST) {
           // histogram sub-form: the statistics come from the class's score histogram, which only
           // a commit to this workgroup changes — no scan of the column, no merge across waves
           WSTAMP(9);
-          hist_publish(pod + 1, nb);
+          ht = hist_publish(pod + 1, nb);
           WSTAMP(10);
         } else {
           const int16_t* c1 = R.cache + s_pcls[(pod + 1) % RING] * chunk;
@@ -833,9 +894,25 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           const int32_t j = k * RT + rt;
           if (M0 >= 0 && j < nrows && (int32_t)c0[j] == M0) {
             uint32_t m2;
-            R.ev2[j] = feval(EC, Q, plus(load_frow<false>(R, j), P), m2);
-            R.rm2[j] = m2;
+            const FRow r2 = plus(load_frow<false>(R, j), P);
+            const int32_t en = feval(EC, Q, r2, m2);
+            if constexpr (HIST) {
+              // the finished fix granule of pod + 1 should pod commit to row j: the class's
+              // statistics with the row moved from its cached evaluation to the post-commit one,
+              // and whether the commit leaves the exact float64 range
+              int32_t Ff, Mf, Cf;
+              khist::fix(ht.f, ht.m1, ht.c1, ht.m2, ht.c2, (int32_t)R.cache[s_pcls[(pod + 1) % RING] * chunk + j], en, &Ff, &Mf, &Cf);
+              const bool stop = (r2.rc >= EXACT_LIM) | (r2.rm >= EXACT_LIM) | (r2.zc >= EXACT_LIM) | (r2.zm >= EXACT_LIM);
+              R.fixg[j] = gpack(ptag(pod + 1), Ff, Cf, Mf) | (stop ? (1ull << 55) : 0ull);
+            } else {
+              R.ev2[j] = en;
+              R.rm2[j] = m2;
+            }
           }
+        }
+        if constexpr (HIST) {  // this wave's granules are in LDS: mark the iteration done for the owner
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+          if (lane == 0) __hip_atomic_store(&s_done[wv - 1], (uint32_t)(pod - a.first + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       } else {
 #pragma unroll
@@ -907,7 +984,15 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
       // ---------------- d. owner: correction of pod + 1's statistics, O(1), then the commit ----
       if (wv == 0) {
         OSTAMP(17);
-        if (has_next) {
+        if constexpr (HIST) {
+          // the fix left before the barrier (section c); the workgroup's own copy of pod + 1's
+          // statistics follows it here, off the chain
+          if (has_next) {
+            hM_old = s_wg[nb][1];
+            hM_new = gscore(hfix);
+            if (lane == 0) { s_wg[nb][0] = gfit(hfix); s_wg[nb][1] = hM_new; s_wg[nb][2] = gcnt(hfix); }
+          }
+        } else if (has_next) {
           if (STREAM && jsel == s_prow[nb]) {  // pod - 1's deferred commit hit this row too
             FRow r = jrow;
             r.rc = s_pval[0]; r.rm = s_pval[1]; r.zc = s_pval[2]; r.zm = s_pval[3]; r.count = s_pcnt;
@@ -918,32 +1003,15 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           if (!STREAM) { e_new = R.ev2[jsel]; m_new = R.rm2[jsel]; }
           // the workgroup's pod + 1 statistics without the committed row's pre-commit
           // evaluation, with its post-commit one (straight-line selects)
-          int32_t e_old, f0, m1 = -1, c1 = 0, m2 = -1, c2 = 0;
-          if constexpr (HIST) {  // read before the barrier: only e_new waited for the row waves
-            e_old = he_old;
-            f0 = hF0;
-          } else {
-            e_old = CACHE ? (int32_t)R.cache[s_pcls[(pod + 1) % RING] * chunk + jsel] : R.ev[nb * chunk + jsel];
-            f0 = s_wg[nb][0]; m1 = s_wg[nb][1]; c1 = s_wg[nb][2]; m2 = s_wg[nb][3]; c2 = s_wg[nb][4];
-          }
+          const int32_t e_old = CACHE ? (int32_t)R.cache[s_pcls[(pod + 1) % RING] * chunk + jsel] : R.ev[nb * chunk + jsel];
+          const int32_t f0 = s_wg[nb][0], m1 = s_wg[nb][1], c1 = s_wg[nb][2], m2 = s_wg[nb][3], c2 = s_wg[nb][4];
           const bool rem = e_old >= 0, add = e_new >= 0;
           const int32_t Ff = f0 - (rem ? 1 : 0) + (add ? 1 : 0);
-          int32_t M, Cn;
-          if constexpr (HIST) {
-            // the class's histogram row with the committed row moved from e_old to e_new in
-            // registers (lane = score): exact, whatever the buckets below the top hold.  (F moves
-            // by the same row: hF0 is the sum of the row as read.)
-            const int32_t h = khist::adjusted(hrow, lane, e_old, e_new);
-            M = khist::top(__ballot(h != 0));
-            Cn = __builtin_amdgcn_readlane(h, M < 0 ? 0 : M);
-            hM_new = M;
-          } else {
-            const int32_t c1a = c1 - ((rem && e_old == m1) ? 1 : 0);
-            const int32_t mb = c1a ? m1 : (c2 ? m2 : -1), cb = c1a ? c1a : c2;
-            const bool up = add && (cb == 0 || e_new > mb), eq = add && !up && e_new == mb;
-            M = up ? e_new : mb;
-            Cn = up ? 1 : cb + (eq ? 1 : 0);
-          }
+          const int32_t c1a = c1 - ((rem && e_old == m1) ? 1 : 0);
+          const int32_t mb = c1a ? m1 : (c2 ? m2 : -1), cb = c1a ? c1a : c2;
+          const bool up = add && (cb == 0 || e_new > mb), eq = add && !up && e_new == mb;
+          const int32_t M = up ? e_new : mb;
+          const int32_t Cn = up ? 1 : cb + (eq ? 1 : 0);
           PROBE(2);
           if (NR > 1 && lane < NR)
             ksimx::store_agent((gu64*)fix_at(granules + lane * REP_STRIDE, (int)((pod + 1) % NSLOT)),
@@ -954,18 +1022,22 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
             s_wg[nb][0] = Ff; s_wg[nb][1] = Cn ? M : -1; s_wg[nb][2] = Cn;
           }
         }
-        OSTAMP(18);
+        if (!HIST) OSTAMP(18);
         if (CACHE) {
           // the committed row's evaluation for every class (lane k = class k), off the critical
           // path: the next pods' statistics read them after the barrier below; HIST: one count
           // moves per class with it
           const FRow r2 = plus(load_frow<false>(R, jsel), load_fpod(s_pod[pod % RING]));
+          int32_t en = -1;
           if (lane < a.ncls) {
             uint32_t rm;
-            const int32_t en = feval(EC, cls_fpod(lane), r2, rm);
+            en = feval(EC, cls_fpod(lane), r2, rm);
             if constexpr (HIST) khist::move(R.hist + lane * KSIM_PHIST_BUCKETS, (int32_t)R.cache[lane * chunk + jsel], en);
             R.cache[lane * chunk + jsel] = (int16_t)en;
           }
+          // HIST: the row's post-commit evaluation for pod + 1's class, for the masks below
+          if (HIST && has_next) e_new = __builtin_amdgcn_readlane(en, __builtin_amdgcn_readfirstlane(s_pcls[(pod + 1) % RING]));
+          if (HIST && (r2.rc >= EXACT_LIM || r2.rm >= EXACT_LIM || r2.zc >= EXACT_LIM || r2.zm >= EXACT_LIM)) stopbit = 1ull << 55;
         }
         if (lane == 0) {  // commit: NodeInfo.AddPod into the LDS row (STREAM: deferred, s_prow)
           if (!STREAM) {
@@ -977,7 +1049,7 @@ __global__ __launch_bounds__(BS) void ksim_pfast_kernel(PfArgs a) {
           if (stopbit) atomicOr(a.err, 8);
           a.out_node[pod] = (int32_t)(a.node_base + lo + jsel);
           if (has_next) {
-            R.ev[nb * chunk + jsel] = e_new;
+            if (!HIST) R.ev[nb * chunk + jsel] = e_new;  // (HIST: fixg lies there)
             s_fix[nb][0] = jsel;
             s_fix[nb][1] = (int32_t)m_new;
           } else {

@@ -8,8 +8,8 @@
 // word `khist::word(s)` atomically and no add carries from one half into the other.
 //
 // Plain inline functions without device intrinsics: the kernel calls them per lane (lane =
-// bucket) or from one lane, and tests/c/phist_check.cpp drives them on the host against a
-// recount.
+// bucket, `fix`: lane = row) or from one lane, and tests/c/phist_check.cpp and
+// tests/c/phist_fix_check.cpp drive them on the host against a recount.
 #pragma once
 #include <stdint.h>
 
@@ -65,6 +65,32 @@ KSIM_PHIST_FN void stats(const uint16_t* row, int e_old, int e_new, int32_t* F, 
   *F = f;
   *M = m;
   *C = m < 0 ? 0 : adjusted(row[m], m, e_old, e_new);
+}
+
+// A test may count how often each case of `fix` below is taken (tests/c/phist_fix_check.cpp).
+#ifndef KSIM_PHIST_TAKEN
+#define KSIM_PHIST_TAKEN(k) ((void)0)
+#endif
+
+// The same (F, M, C) from five numbers of the row instead of the row: F0 its sum, M1 its highest
+// non-empty bucket and C1 that bucket, M2 the highest non-empty bucket below M1 and C2 that one
+// (M1 / M2 = -1 and C1 / C2 = 0 where there is none).  Exact: every bucket above M1 and every
+// bucket strictly between M2 and M1 is empty, so after the row leaves e_old the top is M1 (rows
+// left in it), else M2, else nothing, and e_new then enters above it, into it or below it.
+// M = -1 whenever C = 0.  Straight-line selects: the kernel runs it per lane (lane = row).
+KSIM_PHIST_FN void fix(int32_t F0, int M1, int32_t C1, int M2, int32_t C2, int e_old, int e_new, int32_t* F,
+                       int32_t* M, int32_t* C) {
+  const bool rem = e_old >= 0, add = e_new >= 0;
+  const int32_t c1a = C1 - ((rem && e_old == M1) ? 1 : 0);
+  const int mb = c1a ? M1 : (C2 ? M2 : -1);
+  const int32_t cb = c1a ? c1a : C2;
+  const bool up = add && (cb == 0 || e_new > mb), eq = add && !up && e_new == mb;
+  KSIM_PHIST_TAKEN(c1a != C1 ? 0 : 1);                       // the row left the top bucket / another or none
+  KSIM_PHIST_TAKEN(c1a ? 2 : C2 ? 3 : 4);                    // top kept / second bucket becomes the top / nothing left
+  KSIM_PHIST_TAKEN(!add ? 5 : up ? (cb == 0 ? 6 : 7) : eq ? 8 : 9);  // unfit / into nothing / above / on / below the top
+  *F = F0 - (rem ? 1 : 0) + (add ? 1 : 0);
+  *M = up ? e_new : mb;
+  *C = up ? 1 : cb + (eq ? 1 : 0);
 }
 
 }  // namespace khist
