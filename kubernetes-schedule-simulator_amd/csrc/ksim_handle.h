@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ksim_common.h"
+#include "../../include/ksim_plan.h"
 #include "ksim_pgen.h"
 #include "ksim_sweep.h"
 #include "ksim_tree.h"
@@ -36,7 +37,7 @@ extern "C" hipError_t ksim_launch_serve(const KsimCtx* c, const KsimServeArgs* a
 extern "C" hipError_t ksim_launch_ipa_pass(const KsimCtx* c, int npt, int grid, hipStream_t s);
 extern "C" hipError_t ksim_launch_assume(const KsimCtx* c, int64_t pod, int64_t node, int32_t* status, hipStream_t s);
 extern "C" hipError_t ksim_launch_persistent(const KsimCtx* c, const KsimCtx* cdev, uint64_t* granules, int grid,
-                                             int lds_rows, hipStream_t s);
+                                             int lds_rows, hipStream_t s, ksim_plan_info* plan);
 extern "C" int ksim_persistent_config(int64_t n, int* grid, int* lds_rows);
 extern "C" size_t ksim_persistent_granule_bytes(int grid);
 extern "C" hipError_t ksim_sweep_prepare(const int64_t* ac, const int64_t* am, int64_t n, double* dac, double* dam,
@@ -166,6 +167,7 @@ struct ksim_handle {
   // node table (any other commit path clears it)
   int32_t n_tcls = 0;                      // -1: more classes than the tree supports
   bool last_pfast_cache = false;           // the last fast-kernel call took the cached form
+  ksim_plan_info last_plan = {};           // the last general persistent launch (ksim_last_plan)
   int32_t last_form = 0;                   // KSIM_FORM_* of the last ksim_schedule call (ksim_last_form)
   uint64_t* pick_words = nullptr;          // the per-pod pick kernel's exchange records
   uint32_t pick_tag = 0;

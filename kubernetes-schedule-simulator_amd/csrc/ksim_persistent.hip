@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "../../include/ksim_plan.h"
 #include "ksim_decide.h"
 #include "ksim_fast.h"
 #include "ksim_wave.h"
@@ -1413,7 +1414,7 @@ static size_t static_lds() {
 
 template <int BS, int NPT, int MB>
 static hipError_t launch_persistent(const KsimCtx* c, const KsimCtx* cdev, uint64_t* granules, int grid, int lds_rows,
-                                    hipStream_t s) {
+                                    hipStream_t s, ksim_plan_info* plan) {
   const size_t lds_max = 160 * 1024 - static_lds<BS, NPT, MB>();
   auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
   size_t off = al((size_t)lds_rows * LDS_ROW_BYTES);
@@ -1449,17 +1450,28 @@ static hipError_t launch_persistent(const KsimCtx* c, const KsimCtx* cdev, uint6
   }
   hipError_t e = ksim_check_coresident(ksim_persistent_kernel<BS, NPT, MB>, grid, BS, off);
   if (e != hipSuccess) return e;
+  if (plan) {  // ksim_last_plan
+    plan->kernel = KSIM_PLAN_C2;
+    plan->grid = grid;
+    plan->rows_per_wg = lds_rows;
+    plan->rows_per_thread = NPT;
+    plan->finished = 1;
+    plan->ps = L.ps;
+    plan->tables = L.tables;
+    plan->static_table = L.off_st ? 1 : 0;
+    plan->lds_bytes = (int64_t)off;
+  }
   hipLaunchKernelGGL((ksim_persistent_kernel<BS, NPT, MB>), dim3(grid), dim3(BS), off, s, *c, cdev, granules, L);
   return hipGetLastError();
 }
 
 extern "C" hipError_t ksim_launch_persistent(const KsimCtx* c, const KsimCtx* cdev, uint64_t* granules, int grid,
-                                             int lds_rows, hipStream_t s) {
-  if (grid <= 64 && lds_rows <= 448) return launch_persistent<512, 1, 1>(c, cdev, granules, grid, lds_rows, s);
-  if (lds_rows <= 448) return launch_persistent<512, 1, MAXB>(c, cdev, granules, grid, lds_rows, s);
-  if (lds_rows <= 896) return launch_persistent<512, 2, MAXB>(c, cdev, granules, grid, lds_rows, s);
-  if (lds_rows <= 1792) return launch_persistent<512, 4, MAXB>(c, cdev, granules, grid, lds_rows, s);
-  return launch_persistent<512, 8, MAXB>(c, cdev, granules, grid, lds_rows, s);
+                                             int lds_rows, hipStream_t s, ksim_plan_info* plan) {
+  if (grid <= 64 && lds_rows <= 448) return launch_persistent<512, 1, 1>(c, cdev, granules, grid, lds_rows, s, plan);
+  if (lds_rows <= 448) return launch_persistent<512, 1, MAXB>(c, cdev, granules, grid, lds_rows, s, plan);
+  if (lds_rows <= 896) return launch_persistent<512, 2, MAXB>(c, cdev, granules, grid, lds_rows, s, plan);
+  if (lds_rows <= 1792) return launch_persistent<512, 4, MAXB>(c, cdev, granules, grid, lds_rows, s, plan);
+  return launch_persistent<512, 8, MAXB>(c, cdev, granules, grid, lds_rows, s, plan);
 }
 
 // The fixed table of decision cases: K in {1, 2, 5, 16}; classes without nodes; all-zero class

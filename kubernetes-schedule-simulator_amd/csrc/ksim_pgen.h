@@ -2,6 +2,7 @@
 // inter-pod affinity, SelectorSpread, volumes or CheckServiceAffinity in one launch per call.
 #pragma once
 #include "ksim_common.h"
+#include "ksim_pgen_plan.h"
 
 // ---- per-pod context record (built by ksim_pgen_pack before the launch, one per queued pod) ----
 // Everything the per-pod cycle reads besides the node rows, denormalised from the class, affinity
@@ -114,6 +115,8 @@ struct PGenArgs {
   uint32_t off[PGO_N];
   int32_t has_aff, has_vol;
   int32_t n_zone;     // zones of the spread reduce (<= PG_MAXZ)
+  int32_t ra_words;   // pass-A words a pod of this handle may read: every call writes them all (<= 64)
+  int32_t k_words;    // class words likewise (the most reduce classes of a pod class, <= KSIM_MAX_RCLASS)
   int32_t svc_on;     // CheckServiceAffinity's lender check (A.svc_*; single-hypothesis kernel, n_pair <= PG_SVC_PAIRS)
   uint64_t spin_ticks;
   int32_t test_stall;  // diagnostic (KSIM_PGEN_TEST_STALL): the last workgroup exits at once, as one
@@ -129,4 +132,10 @@ extern "C" size_t ksim_pgen_lds_budget(void);
 extern "C" size_t ksim_pgen_gran_bytes(void);
 extern "C" int ksim_pgen_max_zones(void);
 extern "C" int ksim_pgen_max_aux_domains(void);
+// A pass-A record holds at most 64 words — InterPodAffinity's and SelectorSpread's four, the spread zones,
+// the auxiliary priority's three and its domains — because lane w of the control wave publishes word w.
+// A handle whose pods may read more takes the launch form (pgen_plan).  (Before this was checked the caps
+// were 28 zones and 64 domains apart, 99 words together: lanes 0-63 published, the readers of words 64..
+// ran out their spin bound and the launch form finished the range.)
+#define PG_RA_WORDS 64
 #define PG_SVC_PAIRS 256  // counted pairs whose domain-0 counts a workgroup keeps (the lender check's totals)

@@ -51,8 +51,8 @@
 #define PG_MAXZ 28
 // words of a pass-A record: min, max, max count, haveZones, the spread zone sums, then the
 // auxiliary priority's max count, summed count, haveZones and domain sums
-#define PG_MAXAD 64  // the auxiliary priority's domains
-#define PG_RA (4 + PG_MAXZ + 3 + PG_MAXAD)
+#define PG_RA PG_RA_WORDS  // words of a pass-A record: one lane of the control wave publishes each (ksim_pgen.h)
+#define PG_MAXAD (PG_RA - 4 - 3)  // the auxiliary priority's domains, without spread zones (57); with zones fewer
 #define PG_MAXL 256          // longest counted-pair / carry list of a pod (shared-domain commit)
 // exchange buffer: pass-A records, class granules, then one commit word per slot
 #define PG_COMMIT_OFF ((int64_t)PG_NSLOT * (PG_RA + KSIM_MAX_RCLASS) * PG_MAXG)
@@ -586,13 +586,36 @@ __device__ __forceinline__ void pg_write_back(const KsimCtx& c, const PGenArgs& 
 
 namespace {
 
+// The commit word: only a pod with a shared-domain commit writes it, so its tag is the whole call index
+// + 1 (32 bits above the node index; a launch holds far fewer pods, and the cleared word matches none).
+__device__ __forceinline__ uint64_t pg_commit_word(int64_t idx, int64_t node) {
+  return ((uint64_t)(uint32_t)(idx + 1) << 32) | (uint64_t)(uint32_t)node;
+}
+__device__ __forceinline__ bool pg_commit_is(uint64_t v, int64_t idx) { return (uint32_t)(v >> 32) == (uint32_t)(idx + 1); }
+__device__ __forceinline__ int64_t pg_commit_node(uint64_t v) { return (int64_t)(uint32_t)v; }
+
+// A pod without pass A still writes its tag into every pass-A word of its slot that a pod of this
+// handle may read (g.ra_words, value 0), and a pass-A pod into the words beyond its own: the records
+// are a ring of four slots under an 8-bit tag, so a word left alone would still carry, 256 calls later,
+// the tag the next reader waits for — with the value of the pod 256 calls back, or the zeros the
+// granules are cleared to before the call (tag 0 = call index 255).  Every word written by every call.
+__device__ __forceinline__ void pg_passa_blank(const PGenArgs& g, int slot, uint32_t tag, int lane) {
+  if (lane < g.ra_words) ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | (uint64_t)B55);
+}
+
 // Wave 0 publishes the workgroup's class granules of the pod: lane q folds the waves' partials of
 // class q into tag | fit count (class 0 only) | count at max | max score.
 template <int NW>
 __device__ __forceinline__ void pg_publish_classes(const PGenArgs& g, int K, int slot, uint32_t tag, int lane,
                                                    const int32_t (&s_fit)[NW], const int32_t (&s_mx)[NW][KSIM_MAX_RCLASS],
                                                    const int32_t (&s_cn)[NW][KSIM_MAX_RCLASS]) {
-  if (lane >= K) return;
+  // (every pod writes every class word a pod of this handle may read, g.k_words >= K: a word never
+  // keeps the tag of the pod 256 calls back in its slot)
+  if (lane >= g.k_words) return;
+  if (lane >= K) {
+    ksimx::store_agent(cls_at(g.gran, slot, lane, blockIdx.x), (uint64_t)tag << 56);
+    return;
+  }
   int32_t m = -1, nn = 0, f = 0;
 #pragma unroll
   for (int w = 0; w < NW; ++w) {
@@ -1067,6 +1090,8 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
             s_az[lane - A0 - 3] = 0;
           }
           ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | ((uint64_t)(v + B55) & M56));
+        } else if (lane < g.ra_words) {  // the words this pod does not read: its tag all the same (pg_passa_blank)
+          ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | (uint64_t)B55);
         }
         // sweep every record: lane l reads workgroups l, l + 64, ...; batches of 8 words
         int64_t a_mn = 0, a_mx = 0, a_smx = 0, a_hz = 0, a_amx = 0, a_atot = 0, a_ahz = 0;
@@ -1156,6 +1181,8 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
                                                                                            gahz != 0, gazm));
         }
       }
+    } else if (wv == 0) {
+      pg_passa_blank(g, slot, tag, lane);
     }
     if (aon && ap < 0) {  // serviceAntiAffinity of a pod no service selects: 10 on a labelled row (no pass A)
 #pragma unroll
@@ -1275,7 +1302,7 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
           pg_svc_commit(g, L, Pr.aff_ident, jsel);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         }
-        ksimx::store_agent(g.gran + PG_COMMIT_OFF + slot, ((uint64_t)tag << 56) | (uint64_t)w);
+        ksimx::store_agent(g.gran + PG_COMMIT_OFF + slot, pg_commit_word(pod - c.first, w));
       }
       if (!c.no_commit) {
         // NodeInfo.AddPod on the row (node_info.go:318-341)
@@ -1352,12 +1379,12 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
         // the chosen node, from the owner's commit word
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         uint64_t v;
-        while (gtag(v = ksimx::load_agent(g.gran + PG_COMMIT_OFF + slot)) != tag) {
+        while (!pg_commit_is(v = ksimx::load_agent(g.gran + PG_COMMIT_OFF + slot), pod - c.first)) {
           if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) { atomicOr(c.err, 4); s_abort = 1; break; }
           __builtin_amdgcn_s_sleep(1);
         }
         if (g.svc_on) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (the owner's svc_conflict bits)
-        s_node = (int64_t)(v & M56);
+        s_node = pg_commit_node(v);
       }
       __syncthreads();
       if (s_abort) { stop_pod = pod; break; }
@@ -1414,6 +1441,9 @@ __global__ __launch_bounds__(PG_BS) void ksim_pgen_kernel(KsimCtx c_arg, PGenArg
 #define PG2_NW (PG2_BS / 64)
 #define PG_RT 192  // rows per thread slot: waves 1-3 (E0, the row state), waves 5-7 (E1)
 #define PG_RW 3
+// the host's geometry rules (ksim_pgen_plan.h) are written against these
+static_assert(PG_RT == KSIM_PGP_RT2 && PG_BS == KSIM_PGP_RT1 && PG_MAXG == KSIM_PGP_MAX_GRID && KSIM_PGP_MAX_GRID2 == 64,
+              "ksim_pgen_plan.h constants");
 
 struct PgEv {
   int64_t sc, raw;
@@ -1714,6 +1744,8 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
             s_az[lane - A0 - 3] = 0;
           }
           ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | ((uint64_t)(v + B55) & M56));
+        } else if (lane < g.ra_words) {  // the words this pod does not read: its tag all the same (pg_passa_blank)
+          ksimx::store_agent(rec_at(g.gran, slot, lane, blockIdx.x), ((uint64_t)tag << 56) | (uint64_t)B55);
         }
 #ifdef KSIM_STAMPS
         t_pub = __builtin_amdgcn_s_memtime();
@@ -1821,6 +1853,8 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
                                     (uint64_t)ksim_spread_score(cur[k].cnt, gsmx, ghz != 0, cur[k].zz,
                                                                 cur[k].zz >= 0 ? s_gz[cur[k].zz] : 0, gzm));
       }
+    } else if (wv == 0) {
+      pg_passa_blank(g, slot, tag, lane);
     }
     if (aon && ap < 0) {  // serviceAntiAffinity of a pod no service selects: 10 on a labelled row (no pass A)
 #pragma unroll
@@ -2006,7 +2040,7 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
       c.out_node[pod] = (int32_t)w;
       if (shared) {
         s_node = w;
-        ksimx::store_agent(g.gran + PG_COMMIT_OFF + slot, ((uint64_t)tag << 56) | (uint64_t)w);
+        ksimx::store_agent(g.gran + PG_COMMIT_OFF + slot, pg_commit_word(pod - c.first, w));
       }
     }
     PG_STAMP(4);
@@ -2027,11 +2061,11 @@ __global__ __launch_bounds__(PG2_BS) void ksim_pgen2_kernel(KsimCtx c_arg, PGenA
       if (!owner && tid == 0) {
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         uint64_t v;
-        while (gtag(v = ksimx::load_agent(g.gran + PG_COMMIT_OFF + slot)) != tag) {
+        while (!pg_commit_is(v = ksimx::load_agent(g.gran + PG_COMMIT_OFF + slot), pod - c.first)) {
           if (__builtin_amdgcn_s_memrealtime() - t0 > g.spin_ticks) { atomicOr(c.err, 4); s_abort = 1; break; }
           __builtin_amdgcn_s_sleep(1);
         }
-        s_node = (int64_t)(v & M56);
+        s_node = pg_commit_node(v);
       }
       __syncthreads();
       if (s_abort) { stop_pod = pod; break; }

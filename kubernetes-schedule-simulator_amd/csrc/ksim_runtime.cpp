@@ -852,6 +852,17 @@ static int run_pfast_mode(ksim_handle* h, int64_t first, int64_t count, int grid
   return KSIM_OK;
 }
 
+// The most reduce classes of a pod class of the handle (at most KSIM_MAX_RCLASS: wider pods go to the
+// launch form): the pgen kernels write that many class words of a slot for every pod.
+static int class_words(const ksim_handle* h) {
+  int kw = 1;
+  for (size_t k = 0; k < h->h_n_tt.size(); ++k) {
+    const int K = (h->ctx.w[KSIM_W_TAINT_TOLERATION] ? h->h_n_tt[k] : 1) * (h->ctx.use_na ? h->h_n_na[k] : 1);
+    kw = std::max(kw, std::min(K, KSIM_MAX_RCLASS));
+  }
+  return kw;
+}
+
 // The general persistent kernel (ksim_pgen.hip) for a range with affinity / spread / volume /
 // service-affinity pods: its launch plan, or false when it cannot take the range (the launch form
 // then does).  Everything the cycle touches must fit one workgroup's LDS for <= 1,024 rows and
@@ -859,6 +870,7 @@ static int run_pfast_mode(ksim_handle* h, int64_t first, int64_t count, int grid
 // spread reduce's zones within one record; every pod-context record within PG_REC_MAX.
 struct PgPlan {
   int grid = 0, npt = 0;
+  int ra_words = 0, k_words = 1;  // exchange words every call writes (PGenArgs)
   bool v2 = true;  // the dual-hypothesis kernel (192 rows per thread slot); KSIM_PGEN_V1 selects the single one
   int64_t chunk = 0;
   size_t lds = 0;
@@ -866,13 +878,12 @@ struct PgPlan {
   uint32_t off[PGO_N] = {};
 };
 
-static bool pgen_plan(ksim_handle* h, PgPlan* pl, bool allow_v2 = true) {
+static bool pgen_plan(ksim_handle* h, PgPlan* pl) {
   const KsimCtx& c = h->ctx;
   if (getenv("KSIM_NO_PGEN") || h->pgen_off || h->shard.world > 1 || c.n <= 0) return false;
   const bool aux = ksim_rt_aux_on(h), lender = ksim_rt_svc_lender_on(h);
   // the lender check: its totals' domain-0 copies in every workgroup, single-hypothesis kernel only
   if (lender && h->aff_n_pair > PG_SVC_PAIRS) return false;
-  if (lender) allow_v2 = false;
   int64_t s = 0;
   for (int k : {KSIM_W_LEAST_REQUESTED, KSIM_W_MOST_REQUESTED, KSIM_W_BALANCED, KSIM_W_INTERPOD_AFFINITY,
                 KSIM_W_SELECTOR_SPREAD}) {
@@ -886,10 +897,13 @@ static bool pgen_plan(ksim_handle* h, PgPlan* pl, bool allow_v2 = true) {
   if (s >= ((int64_t)1 << 31)) return false;
   if (h->have_aff) {
     if (c.w[KSIM_W_SELECTOR_SPREAD] && h->aff_n_zone > ksim_pgen_max_zones()) return false;
-    // the auxiliary priority: its domain sums in one pass-A record
-    if (aux && h->aff_h.n_adom > ksim_pgen_max_aux_domains()) return false;
     if (h->pg_max_mp + h->pg_max_car > 512) return false;  // the shared-domain commit's list
+    // the pass-A words a pod may read (one lane of the control wave publishes each): InterPodAffinity's
+    // and SelectorSpread's four, the zones, the auxiliary priority's three and its domains
+    pl->ra_words = 4 + ((c.w[KSIM_W_SELECTOR_SPREAD] && !c.no_prio) ? h->aff_n_zone : 0) + (aux ? 3 + h->aff_h.n_adom : 0);
+    if (pl->ra_words > PG_RA_WORDS) return false;  // (the one cap on zones + auxiliary domains)
   }
+  pl->k_words = class_words(h);  // the class words likewise
   // the pod-context record bound (ksim_pgen.h): the longest list of every kind
   PgHdr b{};
   if (h->have_aff) {
@@ -911,43 +925,29 @@ static bool pgen_plan(ksim_handle* h, PgPlan* pl, bool allow_v2 = true) {
   d.vslots = std::min(d.vcap, PG_VS_LDS);
   d.pslots = c.port_slots;
   if (h->have_aff) { d.n_keys = h->aff_n_keys; d.n_pair = h->aff_n_pair; d.n_carry = h->aff_n_carry; }
-  const size_t budget = ksim_pgen_lds_budget();
-  const int64_t gcap = (h->max_grid > 0 && h->max_grid < 256) ? h->max_grid : 256;
-  int64_t cmin = (c.n + gcap - 1) / gcap;  // at most 256 workgroups (KSIM_MAX_GRID)
-  if (cmin > 1024) return false;
-  // the dual form: at most 64 workgroups (one granule per lane in its sweeps), 768 rows each
-  pl->v2 = allow_v2 && !getenv("KSIM_PGEN_V1") && c.n <= 64 * 768;
-  if (pl->v2) cmin = std::max<int64_t>(cmin, (c.n + 63) / 64);
-  const int64_t rt = pl->v2 ? 192 : 256;  // rows per thread slot
-  d.hyp = pl->v2 ? 1 : 0;
+  // the geometry (ksim_pgen_plan.h): the dual form when it can launch the table, else the single one
+  KsimPgenPlanIn in{};
+  in.n = c.n;
+  in.max_grid = h->max_grid;
+  in.allow_dual = !lender && !getenv("KSIM_PGEN_V1");
   // the dense hypothesis deltas (E1's count lookups in one step), when small
-  const int32_t hdense = (pl->v2 && h->have_aff && !getenv("KSIM_PGEN_NO_HDENSE") &&
-                          (int64_t)d.n_pair * 4 + (int64_t)d.n_carry * 12 <= 16384) ? 1 : 0;
-  int64_t chunk = std::min<int64_t>(std::max<int64_t>(cmin, rt), c.n);
-  if (const char* e = getenv("KSIM_PGEN_CHUNK")) chunk = std::max<int64_t>(cmin, std::min<int64_t>(atoll(e), 4 * rt));
-  for (;;) {
-    d.n_st = c.n_classes_dev;  // the static (pod class, row) words, when they fit
+  in.hdense_ok = h->have_aff && !getenv("KSIM_PGEN_NO_HDENSE") && (int64_t)d.n_pair * 4 + (int64_t)d.n_carry * 12 <= 16384;
+  in.n_st = c.n_classes_dev;  // the static (pod class, row) words, when they fit
+  if (const char* e = getenv("KSIM_PGEN_CHUNK")) in.chunk_hint = std::max<int64_t>(1, atoll(e));
+  in.budget = ksim_pgen_lds_budget();
+  auto bytes = [&](int64_t chunk, bool dual, int32_t n_st, int32_t hdense) {
+    d.hyp = dual ? 1 : 0;
+    d.n_st = n_st;
     d.hdense = hdense;
-    size_t lds = ksim_pgen_plan(chunk, &d, pl->off);
-    if (lds > budget) {
-      d.n_st = 0;
-      lds = ksim_pgen_plan(chunk, &d, pl->off);
-    }
-    if (lds > budget && d.hdense) {
-      d.hdense = 0;
-      lds = ksim_pgen_plan(chunk, &d, pl->off);
-    }
-    if (lds <= budget) {
-      pl->lds = lds;
-      break;
-    }
-    if (chunk <= cmin) return pl->v2 ? pgen_plan(h, pl, false) : false;
-    chunk = std::max<int64_t>(cmin, chunk * 7 / 8);
-  }
-  pl->chunk = chunk;
-  pl->grid = (int)((c.n + chunk - 1) / chunk);
-  if (pl->v2 && pl->grid > 64) return pgen_plan(h, pl, false);
-  pl->npt = chunk <= rt ? 1 : chunk <= 2 * rt ? 2 : 4;
+    return ksim_pgen_plan(chunk, &d, pl->off);
+  };
+  KsimPgenPlanOut o{};
+  if (!ksim_pgen_plan_geometry(in, bytes, &o)) return false;
+  pl->lds = bytes(o.chunk, o.dual, o.n_st, o.hdense);  // (d and pl->off as planned)
+  pl->v2 = o.dual;
+  pl->chunk = o.chunk;
+  pl->grid = o.grid;
+  pl->npt = o.npt;
   pl->d = d;
   return true;
 }
@@ -979,6 +979,8 @@ static int run_pgen_mode(ksim_handle* h, int64_t first, int64_t count, const PgP
   g.has_vol = h->have_vol ? 1 : 0;
   if (h->have_vol) g.V = h->vol_h;
   g.svc_on = ksim_rt_svc_lender_on(h) ? 1 : 0;
+  g.ra_words = pl.ra_words;
+  g.k_words = pl.k_words;
   if (h->have_aff) {
     g.ident_shared = h->aff_ident_shared;
     g.aclass_shared = h->aff_aclass_shared;
@@ -1005,6 +1007,21 @@ static int run_pgen_mode(ksim_handle* h, int64_t first, int64_t count, const PgP
     return ksim_fail(h, KSIM_E_UNSUPPORTED, "persistent launch: %d workgroups cannot be co-resident on this device", pl.grid);
   }
   if (e != hipSuccess) return ksim_fail(h, KSIM_E_DEVICE, "pgen launch: %s", hipGetErrorString(e));
+  {
+    ksim_plan_info& p = h->last_plan;  // ksim_last_plan
+    p = ksim_plan_info{};
+    p.kernel = pl.v2 ? KSIM_PLAN_PGEN_DUAL : KSIM_PLAN_PGEN_SINGLE;
+    p.grid = pl.grid;
+    p.rows_per_wg = (int32_t)pl.chunk;
+    p.rows_per_thread = pl.npt;
+    p.finished = 1;
+    p.n_st = pl.d.n_st;
+    p.hdense = pl.d.hdense;
+    p.vslots = pl.d.vslots;
+    p.vcap = pl.d.vcap;
+    p.rec_stride = pl.d.rec_stride;
+    p.lds_bytes = (int64_t)pl.lds;
+  }
   HIPCHK(h, hipEventRecord(h->ev1, ksim_stream(h)));
   HIPCHK(h, hipStreamSynchronize(ksim_stream(h)));
   float ms = 0.f;
@@ -1063,6 +1080,7 @@ static int run_pgen_mode(ksim_handle* h, int64_t first, int64_t count, const PgP
     err &= ~4;
     HIPCHK(h, hipMemcpy(c.err, &err, 4, hipMemcpyHostToDevice));
     h->pgen_off = true;
+    h->last_plan.finished = 0;
     if (cur < first || cur > end) return ksim_fail(h, KSIM_E_DEVICE, "pgen abort at an impossible pod %lld", (long long)cur);
     if (cur < end) {
       ksim_stats s2{};
@@ -1156,7 +1174,7 @@ static int run_persistent_mode(ksim_handle* h, int64_t first, int64_t count, ksi
   HIPCHK(h, hipMemcpyAsync(h->ctx_dev, &c, sizeof(KsimCtx), hipMemcpyHostToDevice, ksim_stream(h)));
   HIPCHK(h, hipMemsetAsync(h->granules, 0, gb, ksim_stream(h)));
   HIPCHK(h, hipEventRecord(h->ev0, ksim_stream(h)));
-  hipError_t e = ksim_launch_persistent(&c, h->ctx_dev, h->granules, grid, lds_rows, ksim_stream(h));
+  hipError_t e = ksim_launch_persistent(&c, h->ctx_dev, h->granules, grid, lds_rows, ksim_stream(h), &h->last_plan);
   if (e == hipErrorCooperativeLaunchTooLarge) {
     // the grid cannot be co-resident here (a smaller or shared device): the launch form instead
     if (h->cfg.mode != KSIM_MODE_PERSISTENT && h->shard.world == 1) return run_launch_mode(h, first, count, st);
@@ -1348,6 +1366,7 @@ int ksim_schedule(ksim_handle* h, int64_t first, int64_t count, int32_t* out_nod
   HIPCHK(h, hipSetDevice(h->device));
   if (st) memset(st, 0, sizeof *st);
   h->last_form = 0;
+  h->last_plan = ksim_plan_info{};
   if (count == 0) return KSIM_OK;
   KsimCtx& c = h->ctx;
   if (c.n == 0) return ksim_fail(h, KSIM_E_NO_NODES, "no nodes available to schedule pods");
@@ -1569,6 +1588,12 @@ int ksim_read_nodes(ksim_handle* h, ksim_node_state* o) {
     HIPCHK(h, hipMemcpy(o->req_scalar, c.req_scalar, (size_t)c.n_scalar * n * 8, hipMemcpyDeviceToHost));
   if (o->ports && c.port_slots) HIPCHK(h, hipMemcpy(o->ports, c.ports, (size_t)c.port_slots * n * 8, hipMemcpyDeviceToHost));
   if (o->port_count) HIPCHK(h, hipMemcpy(o->port_count, c.port_count, n * 4, hipMemcpyDeviceToHost));
+  return KSIM_OK;
+}
+
+int ksim_last_plan(ksim_handle* h, ksim_plan_info* out) {
+  if (!h || !out) return ksim_fail(h, KSIM_E_INVAL, "ksim_last_plan: null argument");
+  *out = h->last_plan;
   return KSIM_OK;
 }
 

@@ -218,6 +218,17 @@ EXPORTS = ["ksim_abi_version", "ksim_last_error", "ksim_create", "ksim_destroy",
            "ksim_read_volumes", "ksim_grow_volumes", "ksim_sweep_nodes", "ksim_last_form"]
 # ksim_last_form bits (include/ksim.h)
 FORM_FAST, FORM_STREAM, FORM_CACHED, FORM_HIST, FORM_ROWS_SHIFT = 1, 2, 4, 8, 8
+# ksim_last_plan (include/ksim_plan.h: not part of ksim.h's function list, so not in EXPORTS)
+PLAN_NONE, PLAN_C2, PLAN_PGEN_SINGLE, PLAN_PGEN_DUAL = 0, 1, 2, 3
+
+
+class PlanInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("kernel", "grid", "rows_per_wg", "rows_per_thread", "finished", "n_st",
+                                         "hdense", "vslots", "vcap", "rec_stride", "ps", "tables", "static_table",
+                                         "reserved")] + [("lds_bytes", C.c_int64)]
+
+
+assert C.sizeof(PlanInfo) == 64
 IPC_HANDLE_BYTES = 64
 MAX_RANKS = 8
 
@@ -264,6 +275,8 @@ def lib():
     L.ksim_set_counter.argtypes = [C.c_void_p, C.c_uint64]
     L.ksim_selftest.restype = C.c_int
     L.ksim_last_form.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    # include/ksim_plan.h
+    L.ksim_last_plan.argtypes = [C.c_void_p, C.POINTER(PlanInfo)]
     L.ksim_shard_setup.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
     L.ksim_shard_export.argtypes = [C.c_void_p, C.c_void_p]
     L.ksim_shard_connect.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

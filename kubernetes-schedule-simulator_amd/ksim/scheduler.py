@@ -527,6 +527,13 @@ class GenericScheduler:
         self.h.call("ksim_last_form", C.byref(v))
         return v.value
 
+    def last_plan(self):
+        """ksim_last_plan: the launch plan of the last schedule call that ran a general persistent
+        kernel, as a dict of abi.PlanInfo's fields (kernel = abi.PLAN_*; all zero after any other path)."""
+        v = abi.PlanInfo()
+        self.h.call("ksim_last_plan", C.byref(v))
+        return {k: getattr(v, k) for k, _ in abi.PlanInfo._fields_ if k != "reserved"}
+
     def schedule(self, first=0, count=None):
         """Schedule + assume pods [first, first+count) in order.
         Returns (node index per pod (-1 = FitError), reason histograms or None, stats)."""
